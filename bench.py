@@ -14,6 +14,13 @@ A "step" = one forward + backward of the full path for one camera view per rank:
 Workload = BASELINE.json's metric configuration: 1M Gaussians, 1920x1080, 5 motion-blur sub-poses,
 SH degree 3, seeded synthetic scene of SURVEY.md §8d; inputs resident in HBM before timing.
 Weak scaling: every rank renders its own view of the same (replicated) Gaussians.
+
+A plain run only sets up, warms up, times the K steps and prints the line (metric, value, unit, ms_per_step, ...).
+`--full` adds what the headline does not need: the per-stage table and host-stall check, the roofline, the view sweep,
+the secondary scene with its training step, the CPU baseline and the per-rank diagnostics.
+`--dump-outputs DIR` writes what the last timed step computed (image, gradients of every input; a fixed seeded sample of
+the per-Gaussian rows and their sums over all rows) as DIR/<name>.npy, so that two builds can be compared output for
+output on identical inputs.
 """
 import argparse
 import json
@@ -81,6 +88,7 @@ class Workload:
         # SplatfactoDeblurModel owns its own — the headline and the secondary scene have the same shape
         self.hints = gs.ops.FrameHints()
         self.view_key = None
+        self.last_out = None            # the rendered image [H,W,3] of the last step (--dump-outputs)
 
     def warm_until_settled(self, at_least: int, at_most: int = 16) -> int:
         """untimed frames until the adaptive slice budget and the arena have converged (two consecutive frames with the
@@ -122,6 +130,7 @@ class Workload:
                 gs.dp.allreduce_gradients(self.all_params, mode=self.allreduce, force=self.force_exchange)
                 b.record()
                 self.exchange_events.append((a, b))
+            self.last_out = out
             return out
         vms = gs.subpose_viewmats(self.viewmat, self.lin, self.ang, self.times_t)
         # the raw parameters (log-scales, opacity logits) go to the kernels as they are: activations and their backward
@@ -141,6 +150,7 @@ class Workload:
             gs.dp.allreduce_gradients(self.all_params, mode=self.allreduce, force=self.force_exchange)
             b.record()
             self.exchange_events.append((a, b))
+        self.last_out = out
         return loss
 
     def sweep_views(self, n_views: int):
@@ -387,6 +397,57 @@ def train_step_timing(gs, dev, sc, N, W, H, S, steps=5):
     return res
 
 
+DUMP_GAUSSIAN_ROWS = 1 << 16     # per-Gaussian gradients: a fixed sample of this many rows (SH alone is 192 MB at 1M)
+DUMP_PIXELS = 1 << 21            # the image is written whole up to this many pixels (1920x1080 fits), else sampled
+
+
+def _fixed_rows(n: int, k: int, seed: int):
+    """sorted indices of a seeded sample of k of n rows (all rows when n <= k): the same for every run and every build"""
+    if n <= k:
+        return None
+    return torch.randperm(n, generator=torch.Generator().manual_seed(seed))[:k].sort().values
+
+
+def _index_array(idx):
+    """row indices as floats: float32 holds every integer below 2^24 exactly, float64 the rest"""
+    return idx.float() if int(idx.max()) < (1 << 24) else idx.double()
+
+
+def dump_outputs(wl, out_dir) -> dict:
+    """What the last timed step handed its caller — the image and the gradients of every input (raw parameters, view
+    matrix, velocities) — as out_dir/<name>.npy in float32 (at most ~50 MB in all).  Arrays larger than the caps above are
+    reduced to a fixed, seeded sample of their rows, and the sampled row indices are written beside them.  Every
+    per-Gaussian gradient also gets grad_<name>_all_rows (float64): its column sums and sums of magnitudes over ALL rows,
+    so that a row outside the sample still counts -> {name: shape}"""
+    import numpy as np
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    arrays = {}
+    img = wl.last_out.detach()                                  # [H,W,3]
+    pix = _fixed_rows(img.shape[0] * img.shape[1], DUMP_PIXELS, seed=1)
+    if pix is None:
+        arrays["image"] = img
+    else:                                                       # [DUMP_PIXELS,3] of the flattened image
+        arrays["image"] = img.reshape(-1, img.shape[-1])[pix.to(img.device)]
+        arrays["image_pixel_rows"] = _index_array(pix)
+    rows = _fixed_rows(wl.params["means"].shape[0], DUMP_GAUSSIAN_ROWS, seed=2)
+    for k, p in wl.params.items():
+        g = (p.grad if p.grad is not None else torch.zeros_like(p)).detach()
+        arrays["grad_" + k] = g if rows is None else g[rows.to(g.device)]
+        arrays[f"grad_{k}_all_rows"] = torch.stack([g.double().sum(dim=0), g.double().abs().sum(dim=0)])
+    if rows is not None:
+        arrays["gaussian_rows"] = _index_array(rows)
+    for k, p in (("viewmat", wl.viewmat), ("lin_vel", wl.lin), ("ang_vel", wl.ang)):
+        arrays["grad_" + k] = p.grad.detach() if p.grad is not None else torch.zeros_like(p)
+    shapes = {}
+    for name, a in arrays.items():
+        a = a.cpu()
+        a = a if a.dtype == torch.float64 else a.float()
+        np.save(out_dir / f"{name}.npy", a.numpy())
+        shapes[name] = list(a.shape)
+    return shapes
+
+
 def launcher_argv(gpus: int, argv, environ, port=None):
     """`python bench.py --gpus N` without a launcher becomes the launcher: -> the torch.distributed.run command line
     (one rank per GPU over RCCL, rendezvous on 127.0.0.1), or None when this process already is a rank / N == 1."""
@@ -416,19 +477,26 @@ def main():
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--subposes", type=int, default=5, help="motion-blur samples S")
     ap.add_argument("--rs-bands", type=int, default=1, help="rolling-shutter row bands R")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: per-stage table, host-stall check and retries, "
+                         "roofline, view sweep, secondary scene (with its training step), CPU baseline, per-rank "
+                         "diagnostics.  Without it a run sets up, warms up, times the K steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (image, gradients of every input; a "
+                         "fixed seeded sample of the per-Gaussian rows) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU oracle baseline")
     ap.add_argument("--allreduce", default="sparse", choices=["sparse", "allreduce", "rs_ag"],
                     help="DP gradient exchange: row-sparse all-gather (default; dense fallback built in), "
                          "dense all-reduce, or reduce-scatter + all-gather")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the second (fitted-model-like) scene")
+    ap.add_argument("--no-secondary", action="store_true", help="(--full) skip the second (fitted-model-like) scene")
     ap.add_argument("--strict-stall", action="store_true",
-                    help="exit 3 when a host stall above 10 %% of the step survives three timing attempts (always reported in "
-                         "`host_stall_check`)")
+                    help="implies --full; exit 3 when a host stall above 10 %% of the step survives three timing attempts "
+                         "(always reported in `host_stall_check` with --full)")
     ap.add_argument("--view", type=int, default=None,
                     help="diagnostics: time camera K of the view sweep's 16 instead of the headline view (the line says so in "
                          "config.workload; never the headline)")
     ap.add_argument("--no-view-sweep", action="store_true",
-                    help="skip the view sweep (16 cameras cycled through one FrameHints; reported beside the headline)")
+                    help="(--full) skip the view sweep (16 cameras cycled through one FrameHints; reported beside the headline)")
     ap.add_argument("--autograd", action="store_true",
                     help="time the torch.autograd route (ops.render_combined + Tensor.backward) instead of the default "
                          "one-call forward + backward (gsdeblur_amd.render_step); same kernels, more host glue")
@@ -508,20 +576,25 @@ def main():
         ops.profiler = None
         return st
 
-    # timed region: HIP events only around the dominant kernel's launches (two event records per step); every
-    # event record is a barrier packet in the queue, so the full per-stage table is taken in a separate,
-    # untimed pass below
-    ops.profiler = ops.StageProfiler(only={DOMINANT_STAGE})
+    # everything beside the headline (stage table, stall retries, roofline, sweep, secondary scene, CPU baseline, per-rank
+    # diagnostics) runs with --full only; a plain run sets up, warms up, times the K steps and prints the line
+    full = args.full or args.strict_stall
+    # timed region (--full): HIP events only around the dominant kernel's launches (two event records per step) for the
+    # roofline; every event record is a barrier packet in the queue, so the full per-stage table is taken in a separate,
+    # untimed pass below.  A plain run times the steps without any profiler.
+    ops.profiler = ops.StageProfiler(only={DOMINANT_STAGE}) if full else None
     dt = timed_region(wl, args.steps)
-    timed_dom = ops.profiler.summary_ms()
+    timed_dom = ops.profiler.summary_ms() if full else {}
     ops.profiler = None
     exchange_ms = None
     if wl.exchange_events:
         torch.cuda.synchronize()
         ev = wl.exchange_events[-args.steps:]
         exchange_ms = sum(a.elapsed_time(b) for a, b in ev) / len(ev)
+    # what the last timed step computed, before any further (untimed) step overwrites it
+    dumped = dump_outputs(wl, args.dump_outputs) if args.dump_outputs and rank == 0 else None
     n_stage_steps = min(args.steps, 5)
-    stages = stage_pass(wl, n_stage_steps)
+    stages = stage_pass(wl, n_stage_steps) if full else None
     # host stall = step time no stage accounts for (the driver saw 86 ms/step on the secondary scene
     # against 8.7 ms of stages and the line said nothing).  Above 10 % of the step the K steps are timed again (every
     # attempt is reported); a stall that survives three attempts is flagged FAILED in the line (and fails the run with --strict-stall; world 1; with N > 1 the rank skew and the
@@ -533,13 +606,13 @@ def main():
     # toward the fastest); the retries only tell whether a stall repeats
     attempts = [round(dt / args.steps * 1e3, 4)]
     first_issue_trace = list(issue_trace)
-    while (world == 1 and len(attempts) < 3 and
+    while (full and world == 1 and len(attempts) < 3 and
            stall_of(attempts[-1], stages, n_stage_steps, exchange_ms or 0.0) > 0.10 * attempts[-1]):
         ops.profiler = ops.StageProfiler(only={DOMINANT_STAGE})
         dt_again = timed_region(wl, args.steps)
         ops.profiler = None
         attempts.append(round(dt_again / args.steps * 1e3, 4))
-    stall_survives = stall_of(attempts[-1], stages, n_stage_steps, exchange_ms or 0.0) > 0.10 * attempts[-1]
+    stall_survives = full and stall_of(attempts[-1], stages, n_stage_steps, exchange_ms or 0.0) > 0.10 * attempts[-1]
     n_isect = ops.last_num_intersects
     slice_isects = list(ops.last_slice_intersects)
     slice_budget = wl.hints.slice_base()                    # (ops.SLICE_ADAPT: doubles after multi-slice frames)
@@ -556,7 +629,7 @@ def main():
                       "select_overflows": wl.hints.select_overflows}
     rows_with_grad = wl.rows_with_gradient()
     sweep = None
-    if world == 1 and not args.no_view_sweep and args.motion == "se3":
+    if full and world == 1 and not args.no_view_sweep and args.motion == "se3":
         sweep = view_sweep(wl, ops)
         # the same cameras through ONE last-frame memory (what rounds 1-5 did, and what a caller without camera keys gets)
         one = view_sweep(wl, ops, per_camera=False, fixed=sweep.pop("_fixed"))
@@ -568,7 +641,7 @@ def main():
     # second scene (reported beside the headline, never part of `value`): a fitted-model-like distribution in which
     # a large share of the Gaussians receives a gradient and the depth-sliced path needs several slices
     secondary = None
-    if not args.no_secondary and args.scene == "survey":
+    if full and not args.no_secondary and args.scene == "survey":
         del wl, params, step
         torch.cuda.empty_cache()
         w2 = Workload(gs, dev, rank, world, N, W, H, S, R, "trained", args.allreduce, False, args.autograd, args.motion)
@@ -621,7 +694,7 @@ def main():
         torch.cuda.empty_cache()
     # per-rank diagnostics (a SCALE record must explain itself: which rank was slow, what the exchange cost it)
     per_rank = rccl_version = None
-    if world > 1 or args.force_exchange:
+    if full and (world > 1 or args.force_exchange):
         my_ms = dt / args.steps * 1e3
         info = {"rank": rank, "device": torch.cuda.get_device_name(dev), "ms_per_step": round(my_ms, 4),
                 "exchange_ms": None if exchange_ms is None else round(exchange_ms, 4),
@@ -640,10 +713,11 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     ms_per_step = dt / args.steps * 1e3
+    npix = H * W
+    value = world * npix / 1e6 / (ms_per_step / 1e3)
 
-    if rank == 0:
-        npix = H * W
-        value = world * npix / 1e6 / (ms_per_step / 1e3)
+    stall_check = None
+    if rank == 0 and full:
         stage_ms = {k: round(sum(v) / n_stage_steps, 4) for k, v in stages.items()}   # per step (sum over slices)
         host_stall = stall_of(ms_per_step, stages, n_stage_steps, exchange_ms or 0.0)
         stall_check = "ok"
@@ -773,6 +847,20 @@ def main():
                                                                  "lockstep_speedup_8x8") if k in dj}
             except Exception:
                 lane_util = None
+        full_report = {
+            "stage_ms": stage_ms,
+            "host_stall_ms": round(host_stall, 4), "timing_attempts_ms": attempts,
+            # first attempt, per step: ms until the host had issued it (the last entry is the closing synchronize)
+            "host_issue_ms_per_step": first_issue_trace[:65] if host_stall > 0.10 * ms_per_step else None,
+            "timing_attempt_reported": "first (retries only diagnose a host stall; they never replace the value)",
+            "host_stall_check": stall_check,
+            "stage_ms_source": f"{n_stage_steps} extra steps with HIP events around every stage, after the timed region",
+            "roofline": roofline,
+            "lane_utilisation": lane_util,
+        }
+        if world == 1 and not args.no_cpu_baseline:
+            full_report["cpu_baseline"] = guarded_cpu_baseline()
+    if rank == 0:
         line = {
             "metric": "fwd+bwd rasterize MPix/s at 1M Gaussians, 1080p, 5 sub-poses",
             "value": round(value, 3), "unit": "MPix/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -805,22 +893,16 @@ def main():
                        "view_sweep": sweep,
                        "secondary": secondary},
             "exchange_ms": None if exchange_ms is None else round(exchange_ms, 4),
-            "stage_ms": stage_ms,
-            "host_stall_ms": round(host_stall, 4), "timing_attempts_ms": attempts,
-            # first attempt, per step: ms until the host had issued it (the last entry is the closing synchronize)
-            "host_issue_ms_per_step": first_issue_trace[:65] if host_stall > 0.10 * ms_per_step else None,
-            "timing_attempt_reported": "first (retries only diagnose a host stall; they never replace the value)",
-            "host_stall_check": stall_check,
-            "stage_ms_source": f"{n_stage_steps} extra steps with HIP events around every stage, after the timed region",
-            "roofline": roofline,
-            "lane_utilisation": lane_util,
+            "full": full,
         }
-        if world == 1 and not args.no_cpu_baseline:
-            line["cpu_baseline"] = guarded_cpu_baseline()
+        if dumped is not None:
+            line["outputs_dumped"] = {"dir": args.dump_outputs, "arrays": dumped}
+        if full:
+            line.update(full_report)
         print(json.dumps(line), flush=True)
     if world > 1 or args.force_exchange:
         dist.destroy_process_group()
-    if rank == 0 and stall_check.startswith("FAILED"):
+    if rank == 0 and stall_check is not None and stall_check.startswith("FAILED"):
         # the line above carries the verdict (`host_stall_check`) and every attempt; the exit code only follows it on
         # request, so that a slow host still leaves a (flagged) measurement instead of none
         print(f"bench.py: {stall_check}", file=sys.stderr)

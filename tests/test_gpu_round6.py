@@ -561,7 +561,7 @@ def test_bench_runs_every_exchange_mode_over_rccl_at_world_1(dev):
     for i, mode in enumerate(("sparse", "allreduce", "rs_ag")):
         env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(29600 + i + os.getpid() % 300),
                    HSA_ENABLE_IPC_MODE_LEGACY="0")
-        r = subprocess.run([sys.executable, str(root / "bench.py"), "--steps", "5", "--warmup", "2", "--no-cpu-baseline",
+        r = subprocess.run([sys.executable, str(root / "bench.py"), "--full", "--steps", "5", "--warmup", "2", "--no-cpu-baseline",
                             "--no-secondary", "--no-view-sweep", "--force-exchange", "--allreduce", mode, "--gaussians",
                             "300000", "--width", "960", "--height", "544", "--subposes", "3"],
                            capture_output=True, text=True, timeout=600, env=env)
