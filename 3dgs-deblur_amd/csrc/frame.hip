@@ -26,6 +26,28 @@
 #define GS_ERR_WORKSPACE 3
 #define GS_EXPORT extern "C" __attribute__((visibility("default")))
 
+// library-internal forms of three exported entry points with a depth gradient (raster_bwd.hip, raster_rs.hip)
+extern "C" int gs_rasterize_bwd_slice_depth(const float* records, const int* sorted_vals, const int* tile_bins,
+                                            const int* band_edges, const float* background, int S, int R, int H, int W,
+                                            const float* out_T, const int* final_idx, const float* v_img,
+                                            const float* v_alpha, float* bwd_T, float* bwd_B, float* v_records,
+                                            const int* gi_of_e, float* tuples, unsigned char* flags,
+                                            const int* sorted_ids, int n_records, const unsigned char* tile_hot,
+                                            int variant, const float* cmb_scale, float cmb_gamma, float cmb_min_level,
+                                            const float* v_depth, void* stream);
+extern "C" int gs_rasterize_bwd_rs_slice_depth(const float* records, const int* sorted_vals, const int* tile_bins,
+                                               const int* band_edges, const float* background, int S, int H, int W,
+                                               const float* out_T, const int* final_idx, const float* v_img,
+                                               const float* v_alpha, float* bwd_T, float* bwd_B, float* tuples,
+                                               unsigned char* flags, const int* sorted_ids, int n_records, int variant,
+                                               const float* cmb_scale, float cmb_gamma, float cmb_min_level,
+                                               const float* pix_vel, int N, float rolling_shutter_time,
+                                               const float* shared_list_times, const float* v_depth, void* stream);
+extern "C" int gs_reduce_grad_tuples_depth(int n_slice, const unsigned* slice_gi, const unsigned* counts,
+                                           const unsigned* cum_excl, const float* tuples, const unsigned char* flags,
+                                           float* v_records, unsigned char* touched, long long n_isect,
+                                           const float* records, int tuples_per_entry, int depth, void* stream);
+
 namespace {
 
 constexpr int kTile = 16;
@@ -719,11 +741,16 @@ GS_EXPORT int gs_frame_forward(const gs_frame_desc* dp, float* records, unsigned
 // [P*N,12] (plain stores; rows the compositor never touched are left as they are) and touched [P*N] (zeroed by the
 // caller).  Replaces the rasterize_backward part of the fork's autograd.Function (Python original:
 // ops.sliced_backward).  The arena is the forward's; this call allocates behind state->arena_used.
-GS_EXPORT int gs_frame_backward(const gs_frame_state* state, const float* records, const float* background,
-                                const int* band_edges, const float* out_T, const float* v_img, const float* v_alpha,
-                                const float* cmb_scale, float cmb_gamma, float cmb_min_level, int bwd_variant,
-                                float* v_records, unsigned char* touched, const float* pix_vel,
-                                const float* sample_times, void* arena_ptr, long long arena_bytes, void* stream_) {
+// v_depth [S,H,W] (nullable) = d loss / d depth_acc, depth_acc[s] = sum over the blended splats of weight * camera-space
+// depth (the forward's out_depth): non-NULL runs the depth specialisations of the compositors and of the tuple reduce,
+// which leave d loss / d depth in v_records[.., 11] (the projection backward reads it with grad flag 64).  NULL: the
+// launches of gs_frame_backward, byte for byte.
+GS_EXPORT int gs_frame_backward_depth(const gs_frame_state* state, const float* records, const float* background,
+                                      const int* band_edges, const float* out_T, const float* v_img, const float* v_alpha,
+                                      const float* cmb_scale, float cmb_gamma, float cmb_min_level, int bwd_variant,
+                                      float* v_records, unsigned char* touched, const float* pix_vel,
+                                      const float* sample_times, void* arena_ptr, long long arena_bytes,
+                                      const float* v_depth, void* stream_) {
   if (!state || !records || !background || !band_edges || !out_T || !v_img || !v_records || !arena_ptr)
     return GS_ERR_INVALID;
   hipStream_t st = (hipStream_t)stream_;
@@ -759,21 +786,21 @@ GS_EXPORT int gs_frame_backward(const gs_frame_state* state, const float* record
       StageScope sc(ST_RASTER_BWD, st);
       if (state->rolling_shutter_time != 0.f || shared) {
         if (!pix_vel) return GS_ERR_INVALID;
-        CHECK(gs_rasterize_bwd_rs_slice(records, reinterpret_cast<const int*>(base + sl.svals),
+        CHECK(gs_rasterize_bwd_rs_slice_depth(records, reinterpret_cast<const int*>(base + sl.svals),
                                         reinterpret_cast<const int*>(base + sl.bins), band_edges, background, S, H, W, out_T,
                                         reinterpret_cast<const int*>(base + sl.fidx), v_img, v_alpha, bwd_T, bwd_B, tuples,
                                         flags, reinterpret_cast<const int*>(base + sl.sorted_ids),
                                         (int)std::min(n_rec, 2147483647ll), bwd_variant & 256, cmb_scale, cmb_gamma,
                                         cmb_min_level, pix_vel, state->N, state->rolling_shutter_time,
-                                        shared ? sample_times : nullptr, st));
+                                        shared ? sample_times : nullptr, v_depth, st));
       } else
-      CHECK(gs_rasterize_bwd_slice(records, reinterpret_cast<const int*>(base + sl.svals),
+      CHECK(gs_rasterize_bwd_slice_depth(records, reinterpret_cast<const int*>(base + sl.svals),
                                    reinterpret_cast<const int*>(base + sl.bins), band_edges, background, S, R, H, W, out_T,
                                    reinterpret_cast<const int*>(base + sl.fidx), v_img, v_alpha, bwd_T, bwd_B, v_records,
                                    reinterpret_cast<const int*>(base + sl.gi_of_e), tuples, flags,
                                    reinterpret_cast<const int*>(base + sl.sorted_ids), (int)std::min(n_rec, 2147483647ll),
                                    reinterpret_cast<const unsigned char*>(base + sl.tile_hot), bwd_variant, cmb_scale,
-                                   cmb_gamma, cmb_min_level, st));
+                                   cmb_gamma, cmb_min_level, v_depth, st));
     }
     {
       StageScope sc(ST_REDUCE, st);
@@ -783,12 +810,22 @@ GS_EXPORT int gs_frame_backward(const gs_frame_state* state, const float* record
       // against 0.092 ms in the thread form, visit r5_prof) — and costs milliseconds on a slice of millions of small
       // splats (fitted-model-like scene: 5 M Gaussians, 8 tuples each).  The list capacity is all the host knows: the
       // exact count's own choice (few Gaussians with boxes of > 128 tiles), or a band-clipped slice of < 2^19 Gaussians.
-      CHECK(gs_reduce_grad_tuples(sl.n, reinterpret_cast<const unsigned*>(base + sl.slice_gi),
+      CHECK(gs_reduce_grad_tuples_depth(sl.n, reinterpret_cast<const unsigned*>(base + sl.slice_gi),
                                   reinterpret_cast<const unsigned*>(base + sl.counts),
                                   reinterpret_cast<const unsigned*>(base + sl.cum), tuples, flags, v_records, touched,
                                   (sl.wave_per_gaussian || (R > 1 && sl.n < (1 << 19))) ? sl.I : 0, records, (int)tpe,
-                                  st));
+                                  v_depth != nullptr, st));
     }
   }
   return GS_OK;
+}
+
+GS_EXPORT int gs_frame_backward(const gs_frame_state* state, const float* records, const float* background,
+                                const int* band_edges, const float* out_T, const float* v_img, const float* v_alpha,
+                                const float* cmb_scale, float cmb_gamma, float cmb_min_level, int bwd_variant,
+                                float* v_records, unsigned char* touched, const float* pix_vel,
+                                const float* sample_times, void* arena_ptr, long long arena_bytes, void* stream_) {
+  return gs_frame_backward_depth(state, records, background, band_edges, out_T, v_img, v_alpha, cmb_scale, cmb_gamma,
+                                 cmb_min_level, bwd_variant, v_records, touched, pix_vel, sample_times, arena_ptr,
+                                 arena_bytes, nullptr, stream_);
 }

@@ -356,6 +356,7 @@ constexpr int GS_FLAG_UPSTREAM_FOV_CLAMP_GRAD = 1;   // back-propagate through t
 constexpr int GS_FLAG_RAW_QUAT_GRAD = 2;             // no projection of the quaternion gradient through q/|q|
 constexpr int GS_FLAG_NO_NEEDLE_HP = 8;              // skip the double-precision covariance chain of needle Gaussians
 constexpr int GS_FLAG_RS_PIXVEL_GRAD = 16;           // pixel-velocity model, exact rolling shutter: v_records[9..10] = d loss / d pv
+constexpr int GS_FLAG_DEPTH_GRAD = 64;               // v_records[11] = d loss / d camera-space depth (record float 9)
 constexpr float kNeedleRatio = 8.0f;                 // largest / smallest scale above which the chain runs in double
 
 // DEFER (== fp.defer_color, as a template parameter): the SH coefficients are neither loaded nor held — 48 VGPRs of
@@ -501,7 +502,11 @@ struct FusedOut {
   float* pose_partial;    // scratch [blocks][slots][12] of the ordered pose-gradient reduction (with v_viewmats / v_twist)
 };
 
-template <int MAXB>
+// DEPTH (grad flag 64): v_records[.., 11] is d loss / d z, z = the record's camera-space depth — under sub-pose p's
+// viewmat (SE(3) sub-poses) or the mid-exposure one (pixel-velocity model, summed over the P records: the twist gets no
+// depth term).  It enters project_one_bwd as its depth gradient: dz * V[2,:3] to the mean, dz * [mean, 1] to row 2 of
+// the view matrix, through the same ordered pose reduction as every other camera gradient.
+template <int MAXB, bool DEPTH>
 __device__ __forceinline__ void fused_bwd_body(const FusedParams& fp, const float* __restrict__ records,
     const float* __restrict__ v_records, const FusedOut& out, const unsigned char* __restrict__ touched,
     int i, bool live, float* lds, float* __restrict__ blk_acc /*LDS [slots][12], see reduce_vV*/) {
@@ -546,7 +551,7 @@ __device__ __forceinline__ void fused_bwd_body(const FusedParams& fp, const floa
                   fp.in.clip, o, k);
       if (k.geom_ok) {
         float vxy[2] = {0.f, 0.f}, vpv[2] = {0.f, 0.f}, vcon[3] = {0.f, 0.f, 0.f}, v_comp = 0.f;
-        float vr = 0.f, vg = 0.f, vb = 0.f;
+        float vr = 0.f, vg = 0.f, vb = 0.f, vz = 0.f;
         for (int p = 0; p < fp.P; ++p) {
           if (touched && !touched[(size_t)p * fp.N + ii]) continue;
           const float tau = fp.times[p];
@@ -563,6 +568,7 @@ __device__ __forceinline__ void fused_bwd_body(const FusedParams& fp, const floa
           vpv[0] += tau * ga.x; vpv[1] += tau * ga.y;
           if (fp.flags & GS_FLAG_RS_PIXVEL_GRAD) { vpv[0] += gc.y; vpv[1] += gc.z; }   // the compositor's row-time term
           vcon[0] += ga.z; vcon[1] += ga.w; vcon[2] += gb.x;
+          if (DEPTH) vz += gc.w;
         }
         vxs = vxy[0]; vys = vxy[1];
         if (vr != 0.f || vg != 0.f || vb != 0.f) {
@@ -583,7 +589,8 @@ __device__ __forceinline__ void fused_bwd_body(const FusedParams& fp, const floa
         pixel_velocity_bwd(k.pc, k.clamp_x ? k.tx : k.pc[0], k.clamp_y ? k.ty : k.pc[1], k.clamp_x, k.clamp_y, up_clamp,
                            k.rz, fp.in.fx, fp.in.fy, lin, ang, vpv, vpc, vlin, vang);
         vtw[0] = vlin[0]; vtw[1] = vlin[1]; vtw[2] = vlin[2]; vtw[3] = vang[0]; vtw[4] = vang[1]; vtw[5] = vang[2];
-        project_one_bwd(m, c3, Vm, fp.in.fx, fp.in.fy, k, o.comp, vxy, 0.f, vcon, v_comp, vm, vc3, vV, vpc, up_clamp);
+        project_one_bwd(m, c3, Vm, fp.in.fx, fp.in.fy, k, o.comp, vxy, DEPTH ? vz : 0.f, vcon, v_comp, vm, vc3, vV, vpc,
+                        up_clamp);
       }
     }
     if (__syncthreads_or(mine)) {
@@ -633,8 +640,8 @@ __device__ __forceinline__ void fused_bwd_body(const FusedParams& fp, const floa
         vxs += ga.x; vys += ga.y;
         float vcon[3] = {ga.z, ga.w, gb.x};
         float vm1[3], vc31[6];
-        project_one_bwd(m, c3, Vm, fp.in.fx, fp.in.fy, k, o.comp, vxy, 0.f, vcon, v_comp, vm1, vc31, vV, nullptr,
-                        up_clamp);
+        project_one_bwd(m, c3, Vm, fp.in.fx, fp.in.fy, k, o.comp, vxy, DEPTH ? gc.w : 0.f, vcon, v_comp, vm1, vc31, vV,
+                        nullptr, up_clamp);
         for (int j = 0; j < 3; ++j) vm[j] += vm1[j];
         for (int j = 0; j < 6; ++j) vc3[j] += vc31[j];
       }
@@ -670,6 +677,7 @@ __device__ __forceinline__ void fused_bwd_body(const FusedParams& fp, const floa
 // v_records) are the same; only the ill-conditioned part of the chain changes precision.
 // ---------------------------------------------------------------------------
 // work item of the SE(3) model: ONE (needle, sub-pose) pair -> its contribution to v_mean[3] and v_cov3d[6], in double
+template <bool DEPTH>
 __device__ __forceinline__ void needle_item_se3(const FusedParams& fp, const float* __restrict__ records,
                                                 const float* __restrict__ v_records,
                                                 const unsigned char* __restrict__ touched, int i, int p, double out[9]) {
@@ -704,12 +712,14 @@ __device__ __forceinline__ void needle_item_se3(const FusedParams& fp, const flo
   const float4 ga = g4[0], gb = g4[1];
   const double vxy[2] = {ga.x, ga.y}, vcon[3] = {ga.z, ga.w, gb.x};
   const double v_comp = fp.antialiased ? (double)gb.y * (double)load_opacity(fp, i) : 0.0;
+  const double vz = DEPTH ? (double)g4[2].w : 0.0;
   double vV[12];
-  project_one_bwd_t<double>(m, c3d, Vm, fp.in.fx, fp.in.fy, kd, comp, vxy, 0.0, vcon, v_comp, out, out + 3, vV, nullptr,
+  project_one_bwd_t<double>(m, c3d, Vm, fp.in.fx, fp.in.fy, kd, comp, vxy, vz, vcon, v_comp, out, out + 3, vV, nullptr,
                             (fp.flags & GS_FLAG_UPSTREAM_FOV_CLAMP_GRAD) != 0);
 }
 
 // work item of the pixel-velocity model: ONE needle (its P records are one projection: their gradients are summed first)
+template <bool DEPTH>
 __device__ __forceinline__ void needle_item_pixvel(const FusedParams& fp, const float* __restrict__ records,
                                                    const float* __restrict__ v_records,
                                                    const unsigned char* __restrict__ touched, int i, double out[9]) {
@@ -737,7 +747,7 @@ __device__ __forceinline__ void needle_item_pixvel(const FusedParams& fp, const 
   project_ctx_t<double>(m, c3d, Vm, fp.in.fx, fp.in.fy, fp.in.W, fp.in.H, kd);
   kd.clamp_x = k.clamp_x; kd.clamp_y = k.clamp_y;
   const double comp = ::sqrt(fmax(0.0, kd.det0 / kd.det));
-  double vxy[2] = {0., 0.}, vcon[3] = {0., 0., 0.}, v_comp = 0.;
+  double vxy[2] = {0., 0.}, vcon[3] = {0., 0., 0.}, v_comp = 0., vz = 0.;
   float vpv[2] = {0.f, 0.f};
   for (int p = 0; p < fp.P; ++p) {
     if (touched && !touched[(size_t)p * fp.N + i]) continue;
@@ -752,6 +762,7 @@ __device__ __forceinline__ void needle_item_pixvel(const FusedParams& fp, const 
     vpv[0] += fp.times[p] * ga.x; vpv[1] += fp.times[p] * ga.y;
     if (fp.flags & GS_FLAG_RS_PIXVEL_GRAD) { vpv[0] += gc.y; vpv[1] += gc.z; }
     vcon[0] += ga.z; vcon[1] += ga.w; vcon[2] += gb.x;
+    if (DEPTH) vz += (double)gc.w;
   }
   const float lin[3] = {fp.twist[0], fp.twist[1], fp.twist[2]}, ang[3] = {fp.twist[3], fp.twist[4], fp.twist[5]};
   float vpc[3], vlin[3], vang[3];
@@ -760,7 +771,7 @@ __device__ __forceinline__ void needle_item_pixvel(const FusedParams& fp, const 
                      vlin, vang);
   const double vpcd[3] = {vpc[0], vpc[1], vpc[2]};
   double vV[12];
-  project_one_bwd_t<double>(m, c3d, Vm, fp.in.fx, fp.in.fy, kd, comp, vxy, 0.0, vcon, v_comp, out, out + 3, vV, vpcd,
+  project_one_bwd_t<double>(m, c3d, Vm, fp.in.fx, fp.in.fy, kd, comp, vxy, vz, vcon, v_comp, out, out + 3, vV, vpcd,
                             (fp.flags & GS_FLAG_UPSTREAM_FOV_CLAMP_GRAD) != 0);
 }
 
@@ -772,87 +783,101 @@ __device__ __forceinline__ void needle_item_pixvel(const FusedParams& fp, const 
 // order (deterministic) before it runs the covariance -> scale / quaternion step and writes the three rows.
 constexpr int kNeedleChunk = 2048;
 
-__global__ __launch_bounds__(256) void project_needle_hp_kernel(FusedParams fp, const float* __restrict__ records,
-    const float* __restrict__ v_records, float* __restrict__ v_means, float* __restrict__ v_scales,
-    float* __restrict__ v_quats, const unsigned char* __restrict__ touched, float ratio_limit) {
-  __shared__ int list[kNeedleChunk];
-  __shared__ int n_list;
-  __shared__ double part[256][9];
-  if (threadIdx.x == 0) n_list = 0;
-  __syncthreads();
-  const int i0 = blockIdx.x * kNeedleChunk + (int)threadIdx.x * 8;
-  if (i0 < fp.N) {
-    unsigned long long any = ~0ull;
-    if (touched) {
-      any = 0ull;
-      const bool word = (fp.N % 8) == 0 && i0 + 8 <= fp.N;
-      for (int p = 0; p < fp.P; ++p) {
-        const unsigned char* t = touched + (size_t)p * fp.N + i0;
-        if (word) any |= *reinterpret_cast<const unsigned long long*>(t);
-        else for (int j = 0; j < 8 && i0 + j < fp.N; ++j) any |= (unsigned long long)t[j] << (8 * j);
-      }
-    }
-    if (any != 0ull) {
-      for (int j = 0; j < 8 && i0 + j < fp.N; ++j) {
-        if (((any >> (8 * j)) & 0xFFull) == 0ull) continue;
-        const int i = i0 + j;
-        // (log-scales: the ratio test in the log domain needs no exp)
-        const float s0 = fp.scales[3 * i], s1 = fp.scales[3 * i + 1], s2 = fp.scales[3 * i + 2];
-        const float smax = fmaxf(s0, fmaxf(s1, s2)), smin = fminf(s0, fminf(s1, s2));
-        const bool needle = (fp.act & GS_ACT_LOG_SCALES) ? (smax - smin > __logf(ratio_limit)) : (smax > ratio_limit * smin);
-        if (needle) list[atomicAdd(&n_list, 1)] = i;
-      }
-    }
-  }
-  __syncthreads();
-  const int n = n_list;
-  if (n == 0) return;
-  const int items_per = fp.pixvel ? 1 : fp.P;                  // <= 256 (kMaxSubposes)
-  const int per_round = max(1, 256 / items_per);               // needles per round
-  for (int base = 0; base < n; base += per_round) {
-    const int cnt = min(per_round, n - base);
-    const int a = (int)threadIdx.x / items_per, p = (int)threadIdx.x - a * items_per;
-    if (a < cnt) {
-      double o9[9];
-      if (fp.pixvel) needle_item_pixvel(fp, records, v_records, touched, list[base + a], o9);
-      else needle_item_se3(fp, records, v_records, touched, list[base + a], p, o9);
-#pragma unroll
-      for (int j = 0; j < 9; ++j) part[threadIdx.x][j] = o9[j];
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < cnt) {
-      const int i = list[base + threadIdx.x];
-      double acc[9] = {0., 0., 0., 0., 0., 0., 0., 0., 0.};
-      for (int pp = 0; pp < items_per; ++pp)
-#pragma unroll
-        for (int j = 0; j < 9; ++j) acc[j] += part[threadIdx.x * items_per + pp][j];
-      float s[3];
-  load_scales(fp, i, s);
-      const float q[4] = {fp.quats[4 * i], fp.quats[4 * i + 1], fp.quats[4 * i + 2], fp.quats[4 * i + 3]};
-      double vs[3], vq[4];
-      cov3d_bwd_t<double>(s, fp.glob, q, acc + 3, vs, vq, (fp.flags & GS_FLAG_RAW_QUAT_GRAD) != 0);
-      if (fp.act & GS_ACT_LOG_SCALES) { vs[0] *= (double)s[0]; vs[1] *= (double)s[1]; vs[2] *= (double)s[2]; }
-      for (int j = 0; j < 3; ++j) { v_means[3 * i + j] = (float)acc[j]; v_scales[3 * i + j] = (float)vs[j]; }
-      for (int j = 0; j < 4; ++j) v_quats[4 * i + j] = (float)vq[j];
-    }
-    __syncthreads();
-  }
+// ONE source for project_needle_hp_kernel and its depth twin project_needle_hp_depth_kernel (grad flag 64:
+// v_records[.., 11] enters the means' double-precision chain too), instantiated by this macro (default kernel: same name,
+// same instruction stream)
+#define GS_NEEDLE_HP_KERNEL(NAME, DEPTH)                                                                                \
+__global__ __launch_bounds__(256) void NAME(FusedParams fp, const float* __restrict__ records,                          \
+    const float* __restrict__ v_records, float* __restrict__ v_means, float* __restrict__ v_scales,                    \
+    float* __restrict__ v_quats, const unsigned char* __restrict__ touched, float ratio_limit) {                       \
+  __shared__ int list[kNeedleChunk];                                                                                          \
+  __shared__ int n_list;                                                                                                      \
+  __shared__ double part[256][9];                                                                                             \
+  if (threadIdx.x == 0) n_list = 0;                                                                                           \
+  __syncthreads();                                                                                                            \
+  const int i0 = blockIdx.x * kNeedleChunk + (int)threadIdx.x * 8;                                                            \
+  if (i0 < fp.N) {                                                                                                            \
+    unsigned long long any = ~0ull;                                                                                           \
+    if (touched) {                                                                                                            \
+      any = 0ull;                                                                                                             \
+      const bool word = (fp.N % 8) == 0 && i0 + 8 <= fp.N;                                                                    \
+      for (int p = 0; p < fp.P; ++p) {                                                                                        \
+        const unsigned char* t = touched + (size_t)p * fp.N + i0;                                                             \
+        if (word) any |= *reinterpret_cast<const unsigned long long*>(t);                                                     \
+        else for (int j = 0; j < 8 && i0 + j < fp.N; ++j) any |= (unsigned long long)t[j] << (8 * j);                         \
+      }                                                                                                                       \
+    }                                                                                                                         \
+    if (any != 0ull) {                                                                                                        \
+      for (int j = 0; j < 8 && i0 + j < fp.N; ++j) {                                                                          \
+        if (((any >> (8 * j)) & 0xFFull) == 0ull) continue;                                                                   \
+        const int i = i0 + j;                                                                                                 \
+        /* (log-scales: the ratio test in the log domain needs no exp) */                                                     \
+        const float s0 = fp.scales[3 * i], s1 = fp.scales[3 * i + 1], s2 = fp.scales[3 * i + 2];                              \
+        const float smax = fmaxf(s0, fmaxf(s1, s2)), smin = fminf(s0, fminf(s1, s2));                                         \
+        const bool needle = (fp.act & GS_ACT_LOG_SCALES) ? (smax - smin > __logf(ratio_limit)) : (smax > ratio_limit * smin); \
+        if (needle) list[atomicAdd(&n_list, 1)] = i;                                                                          \
+      }                                                                                                                       \
+    }                                                                                                                         \
+  }                                                                                                                           \
+  __syncthreads();                                                                                                            \
+  const int n = n_list;                                                                                                       \
+  if (n == 0) return;                                                                                                         \
+  const int items_per = fp.pixvel ? 1 : fp.P;                  /* <= 256 (kMaxSubposes) */                                    \
+  const int per_round = max(1, 256 / items_per);               /* needles per round */                                        \
+  for (int base = 0; base < n; base += per_round) {                                                                           \
+    const int cnt = min(per_round, n - base);                                                                                 \
+    const int a = (int)threadIdx.x / items_per, p = (int)threadIdx.x - a * items_per;                                         \
+    if (a < cnt) {                                                                                                            \
+      double o9[9];                                                                                                           \
+      if (fp.pixvel) needle_item_pixvel<DEPTH>(fp, records, v_records, touched, list[base + a], o9);                          \
+      else needle_item_se3<DEPTH>(fp, records, v_records, touched, list[base + a], p, o9);                                    \
+_Pragma("unroll")                                                                                                             \
+      for (int j = 0; j < 9; ++j) part[threadIdx.x][j] = o9[j];                                                               \
+    }                                                                                                                         \
+    __syncthreads();                                                                                                          \
+    if ((int)threadIdx.x < cnt) {                                                                                             \
+      const int i = list[base + threadIdx.x];                                                                                 \
+      double acc[9] = {0., 0., 0., 0., 0., 0., 0., 0., 0.};                                                                   \
+      for (int pp = 0; pp < items_per; ++pp)                                                                                  \
+_Pragma("unroll")                                                                                                             \
+        for (int j = 0; j < 9; ++j) acc[j] += part[threadIdx.x * items_per + pp][j];                                          \
+      float s[3];                                                                                                             \
+  load_scales(fp, i, s);                                                                                                      \
+      const float q[4] = {fp.quats[4 * i], fp.quats[4 * i + 1], fp.quats[4 * i + 2], fp.quats[4 * i + 3]};                    \
+      double vs[3], vq[4];                                                                                                    \
+      cov3d_bwd_t<double>(s, fp.glob, q, acc + 3, vs, vq, (fp.flags & GS_FLAG_RAW_QUAT_GRAD) != 0);                           \
+      if (fp.act & GS_ACT_LOG_SCALES) { vs[0] *= (double)s[0]; vs[1] *= (double)s[1]; vs[2] *= (double)s[2]; }                \
+      for (int j = 0; j < 3; ++j) { v_means[3 * i + j] = (float)acc[j]; v_scales[3 * i + j] = (float)vs[j]; }                 \
+      for (int j = 0; j < 4; ++j) v_quats[4 * i + j] = (float)vq[j];                                                          \
+    }                                                                                                                         \
+    __syncthreads();                                                                                                          \
+  }                                                                                                                           \
 }
 
-// dense launch: one thread per Gaussian (no touched flags: every Gaussian gets its gradient written)
-template <int MAXB>
-__global__ __launch_bounds__(256) void project_fused_bwd_kernel(FusedParams fp, const float* __restrict__ records,
-    const float* __restrict__ v_records, FusedOut out) {
-  __shared__ float lds[48];
-  extern __shared__ float blk_acc[];             // [slots][12]: this block's pose-gradient sums (reduce_vV)
-  const int slots = out.pose_partial ? (fp.pixvel ? 2 : fp.P) : 0;
-  for (int k = threadIdx.x; k < slots * 12; k += 256) blk_acc[k] = 0.f;
-  __syncthreads();
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  fused_bwd_body<MAXB>(fp, records, v_records, out, nullptr, i, i < fp.N, lds, blk_acc);
-  __syncthreads();
-  for (int k = threadIdx.x; k < slots * 12; k += 256) out.pose_partial[(size_t)blockIdx.x * slots * 12 + k] = blk_acc[k];
+GS_NEEDLE_HP_KERNEL(project_needle_hp_kernel, false)
+GS_NEEDLE_HP_KERNEL(project_needle_hp_depth_kernel, true)
+
+// dense launch: one thread per Gaussian (no touched flags: every Gaussian gets its gradient written).  ONE source for
+// project_fused_bwd_kernel and its depth twin project_fused_bwd_depth_kernel (grad flag 64: v_records[.., 11] = d loss /
+// d depth), instantiated by this macro: the default kernel keeps its name and instruction stream (a shared __device__
+// body changes the latter)
+#define GS_FUSED_BWD_KERNEL(NAME, DEPTH)                                                                                \
+template <int MAXB>                                                                                                     \
+__global__ __launch_bounds__(256) void NAME(FusedParams fp, const float* __restrict__ records,                          \
+    const float* __restrict__ v_records, FusedOut out) {                                                                \
+  __shared__ float lds[48];                                                                                               \
+  extern __shared__ float blk_acc[];             /* [slots][12]: this block's pose-gradient sums (reduce_vV) */           \
+  const int slots = out.pose_partial ? (fp.pixvel ? 2 : fp.P) : 0;                                                        \
+  for (int k = threadIdx.x; k < slots * 12; k += 256) blk_acc[k] = 0.f;                                                   \
+  __syncthreads();                                                                                                        \
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;                                                                    \
+  fused_bwd_body<MAXB, DEPTH>(fp, records, v_records, out, nullptr, i, i < fp.N, lds, blk_acc);                           \
+  __syncthreads();                                                                                                        \
+  for (int k = threadIdx.x; k < slots * 12; k += 256) out.pose_partial[(size_t)blockIdx.x * slots * 12 + k] = blk_acc[k]; \
 }
+
+GS_FUSED_BWD_KERNEL(project_fused_bwd_kernel, false)
+GS_FUSED_BWD_KERNEL(project_fused_bwd_depth_kernel, true)
 
 // sparse launch (touched flags): under early termination ~1 % of the Gaussians carry a gradient and they are
 // scattered, so with one thread per Gaussian nearly every wave ran the whole body for one or two lanes.  A block owns
@@ -879,58 +904,63 @@ __device__ __forceinline__ void zero_rows(float* __restrict__ base, size_t first
 // (256, 2): two waves per SIMD = at most 256 VGPRs.  The body sits right at that cliff (256 with the round-3 pixel-
 // velocity VJP, 258 with round 4's — one wave per SIMD, and the zero fill of the 236 MB of gradient outputs, which is
 // most of this kernel's time on a sparse frame, dropped from 3.3 to 2.3 TB/s: 72 -> 104 us, found by an on-GPU bisect)
-template <int MAXB, bool ZERO_FILL>
-__global__ __launch_bounds__(256, 2) void project_fused_bwd_sparse_kernel(FusedParams fp,
-    const float* __restrict__ records, const float* __restrict__ v_records, FusedOut out,
-    const unsigned char* __restrict__ touched /* [P*N] */) {
-  __shared__ float lds[48];
-  __shared__ int list[kFusedChunk];
-  __shared__ int wave_cnt[4];
-  extern __shared__ float blk_acc[];             // [slots][12]: this block's pose-gradient sums (reduce_vV)
-  const int slots = out.pose_partial ? (fp.pixvel ? 2 : fp.P) : 0;
-  for (int k = threadIdx.x; k < slots * 12; k += 256) blk_acc[k] = 0.f;
-  const int lane = lane_id(), wave = threadIdx.x >> 6;
-  const int base = blockIdx.x * kFusedChunk;
-  if (ZERO_FILL) {
-    const size_t g0 = (size_t)base, cnt = (size_t)min(kFusedChunk, fp.N - base);
-    zero_rows(out.v_means, 3 * g0, 3 * cnt);
-    zero_rows(out.v_scales, 3 * g0, 3 * cnt);
-    zero_rows(out.v_quats, 4 * g0, 4 * cnt);
-    zero_rows(out.v_opac, g0, cnt);
-    if (out.v_sh_rest) {
-      zero_rows(out.v_sh, 3 * g0, 3 * cnt);
-      zero_rows(out.v_sh_rest, (size_t)(fp.K_stride - 1) * 3 * g0, (size_t)(fp.K_stride - 1) * 3 * cnt);
-    } else {
-      zero_rows(out.v_sh, (size_t)fp.K_stride * 3 * g0, (size_t)fp.K_stride * 3 * cnt);
-    }
-    zero_rows(out.v_xy_sum, 2 * g0, 2 * cnt);
-    // the rows of this block's touched Gaussians are written again below, by other threads of the block
-    __threadfence_block();
-  }
-  int n_list = 0;
-  for (int r = 0; r < kFusedChunk / 256; ++r) {
-    const int g = base + r * 256 + (int)threadIdx.x;
-    bool any = false;
-    if (g < fp.N)
-      for (int p = 0; p < fp.P; ++p) any |= touched[(size_t)p * fp.N + g] != 0;
-    const unsigned long long bal = __ballot(any);
-    if (lane == 0) wave_cnt[wave] = __popcll(bal);
-    __syncthreads();
-    int off = n_list, total = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) { const int c = wave_cnt[w]; if (w < wave) off += c; total += c; }
-    if (any) list[off + __popcll(bal & ((1ull << lane) - 1ull))] = g;
-    n_list += total;
-    __syncthreads();
-  }
-  for (int k0 = 0; k0 < n_list; k0 += 256) {
-    const int k = k0 + (int)threadIdx.x;
-    const bool live = k < n_list;
-    fused_bwd_body<MAXB>(fp, records, v_records, out, touched, live ? list[k] : 0, live, lds, blk_acc);
-  }
-  __syncthreads();
-  for (int k = threadIdx.x; k < slots * 12; k += 256) out.pose_partial[(size_t)blockIdx.x * slots * 12 + k] = blk_acc[k];
+// ONE source for project_fused_bwd_sparse_kernel and its depth twin project_fused_bwd_sparse_depth_kernel (grad flag 64)
+#define GS_FUSED_BWD_SPARSE_KERNEL(NAME, DEPTH)                                                                         \
+template <int MAXB, bool ZERO_FILL>                                                                                     \
+__global__ __launch_bounds__(256, 2) void NAME(FusedParams fp,                                                          \
+    const float* __restrict__ records, const float* __restrict__ v_records, FusedOut out,                               \
+    const unsigned char* __restrict__ touched /* [P*N] */) {                                                            \
+  __shared__ float lds[48];                                                                                               \
+  __shared__ int list[kFusedChunk];                                                                                       \
+  __shared__ int wave_cnt[4];                                                                                             \
+  extern __shared__ float blk_acc[];             /* [slots][12]: this block's pose-gradient sums (reduce_vV) */           \
+  const int slots = out.pose_partial ? (fp.pixvel ? 2 : fp.P) : 0;                                                        \
+  for (int k = threadIdx.x; k < slots * 12; k += 256) blk_acc[k] = 0.f;                                                   \
+  const int lane = lane_id(), wave = threadIdx.x >> 6;                                                                    \
+  const int base = blockIdx.x * kFusedChunk;                                                                              \
+  if (ZERO_FILL) {                                                                                                        \
+    const size_t g0 = (size_t)base, cnt = (size_t)min(kFusedChunk, fp.N - base);                                          \
+    zero_rows(out.v_means, 3 * g0, 3 * cnt);                                                                              \
+    zero_rows(out.v_scales, 3 * g0, 3 * cnt);                                                                             \
+    zero_rows(out.v_quats, 4 * g0, 4 * cnt);                                                                              \
+    zero_rows(out.v_opac, g0, cnt);                                                                                       \
+    if (out.v_sh_rest) {                                                                                                  \
+      zero_rows(out.v_sh, 3 * g0, 3 * cnt);                                                                               \
+      zero_rows(out.v_sh_rest, (size_t)(fp.K_stride - 1) * 3 * g0, (size_t)(fp.K_stride - 1) * 3 * cnt);                  \
+    } else {                                                                                                              \
+      zero_rows(out.v_sh, (size_t)fp.K_stride * 3 * g0, (size_t)fp.K_stride * 3 * cnt);                                   \
+    }                                                                                                                     \
+    zero_rows(out.v_xy_sum, 2 * g0, 2 * cnt);                                                                             \
+    /* the rows of this block's touched Gaussians are written again below, by other threads of the block */               \
+    __threadfence_block();                                                                                                \
+  }                                                                                                                       \
+  int n_list = 0;                                                                                                         \
+  for (int r = 0; r < kFusedChunk / 256; ++r) {                                                                           \
+    const int g = base + r * 256 + (int)threadIdx.x;                                                                      \
+    bool any = false;                                                                                                     \
+    if (g < fp.N)                                                                                                         \
+      for (int p = 0; p < fp.P; ++p) any |= touched[(size_t)p * fp.N + g] != 0;                                           \
+    const unsigned long long bal = __ballot(any);                                                                         \
+    if (lane == 0) wave_cnt[wave] = __popcll(bal);                                                                        \
+    __syncthreads();                                                                                                      \
+    int off = n_list, total = 0;                                                                                          \
+_Pragma("unroll")                                                                                                         \
+    for (int w = 0; w < 4; ++w) { const int c = wave_cnt[w]; if (w < wave) off += c; total += c; }                        \
+    if (any) list[off + __popcll(bal & ((1ull << lane) - 1ull))] = g;                                                     \
+    n_list += total;                                                                                                      \
+    __syncthreads();                                                                                                      \
+  }                                                                                                                       \
+  for (int k0 = 0; k0 < n_list; k0 += 256) {                                                                              \
+    const int k = k0 + (int)threadIdx.x;                                                                                  \
+    const bool live = k < n_list;                                                                                         \
+    fused_bwd_body<MAXB, DEPTH>(fp, records, v_records, out, touched, live ? list[k] : 0, live, lds, blk_acc);            \
+  }                                                                                                                       \
+  __syncthreads();                                                                                                        \
+  for (int k = threadIdx.x; k < slots * 12; k += 256) out.pose_partial[(size_t)blockIdx.x * slots * 12 + k] = blk_acc[k]; \
 }
+
+GS_FUSED_BWD_SPARSE_KERNEL(project_fused_bwd_sparse_kernel, false)
+GS_FUSED_BWD_SPARSE_KERNEL(project_fused_bwd_sparse_depth_kernel, true)
 
 // Lazy records (round 5): the records of the n_slice (sub-pose, Gaussian) pairs a depth slice holds — pair j is depth
 // rank slice_rank(sd, j) of sorted_gi, the walk gs_slice_counts_exact makes right afterwards — projected by the SAME
@@ -1277,9 +1307,19 @@ static int launch_fused_bwd(const FusedParams& fp, int sh_degree, const float* r
     out.pose_partial = reinterpret_cast<float*>(scratch);
   }
   dim3 grid(touched ? (N + kFusedChunk - 1) / kFusedChunk : (N + 255) / 256);
+  const bool depth = (fp.flags & GS_FLAG_DEPTH_GRAD) != 0;
   if (touched) {
     const bool zf = (fp.flags & GS_FLAG_ZERO_FILL) != 0;
-    if (sh_degree <= 3 && zf)
+    if (depth) {
+      if (sh_degree <= 3 && zf)
+        hipLaunchKernelGGL((project_fused_bwd_sparse_depth_kernel<16, true>), grid, block, lds, st, fp, records, v_records, out, touched);
+      else if (sh_degree <= 3)
+        hipLaunchKernelGGL((project_fused_bwd_sparse_depth_kernel<16, false>), grid, block, lds, st, fp, records, v_records, out, touched);
+      else if (zf)
+        hipLaunchKernelGGL((project_fused_bwd_sparse_depth_kernel<25, true>), grid, block, lds, st, fp, records, v_records, out, touched);
+      else
+        hipLaunchKernelGGL((project_fused_bwd_sparse_depth_kernel<25, false>), grid, block, lds, st, fp, records, v_records, out, touched);
+    } else if (sh_degree <= 3 && zf)
       hipLaunchKernelGGL((project_fused_bwd_sparse_kernel<16, true>), grid, block, lds, st, fp, records, v_records, out, touched);
     else if (sh_degree <= 3)
       hipLaunchKernelGGL((project_fused_bwd_sparse_kernel<16, false>), grid, block, lds, st, fp, records, v_records, out, touched);
@@ -1288,7 +1328,11 @@ static int launch_fused_bwd(const FusedParams& fp, int sh_degree, const float* r
     else
       hipLaunchKernelGGL((project_fused_bwd_sparse_kernel<25, false>), grid, block, lds, st, fp, records, v_records, out, touched);
   } else {
-    if (sh_degree <= 3)
+    if (depth && sh_degree <= 3)
+      hipLaunchKernelGGL(project_fused_bwd_depth_kernel<16>, grid, block, lds, st, fp, records, v_records, out);
+    else if (depth)
+      hipLaunchKernelGGL(project_fused_bwd_depth_kernel<25>, grid, block, lds, st, fp, records, v_records, out);
+    else if (sh_degree <= 3)
       hipLaunchKernelGGL(project_fused_bwd_kernel<16>, grid, block, lds, st, fp, records, v_records, out);
     else
       hipLaunchKernelGGL(project_fused_bwd_kernel<25>, grid, block, lds, st, fp, records, v_records, out);
@@ -1301,8 +1345,14 @@ static int launch_fused_bwd(const FusedParams& fp, int sh_degree, const float* r
   }
   if (!(fp.flags & GS_FLAG_NO_NEEDLE_HP))
     // needles (scale ratio above kNeedleRatio) get their means / scales / quaternion gradients again, in double
-    hipLaunchKernelGGL(project_needle_hp_kernel, dim3((N + kNeedleChunk - 1) / kNeedleChunk), dim3(256), 0, st, fp, records,
-                       v_records, out.v_means, out.v_scales, out.v_quats, touched, kNeedleRatio);
+  {
+    if (depth)
+      hipLaunchKernelGGL(project_needle_hp_depth_kernel, dim3((N + kNeedleChunk - 1) / kNeedleChunk), dim3(256), 0, st, fp,
+                         records, v_records, out.v_means, out.v_scales, out.v_quats, touched, kNeedleRatio);
+    else
+      hipLaunchKernelGGL(project_needle_hp_kernel, dim3((N + kNeedleChunk - 1) / kNeedleChunk), dim3(256), 0, st, fp,
+                         records, v_records, out.v_means, out.v_scales, out.v_quats, touched, kNeedleRatio);
+  }
   return gs_launch_status();
 }
 

@@ -286,9 +286,13 @@ constexpr int kRsComp = 11;
 constexpr int kRsGroup = 4;
 constexpr int kRsCols = 32, kRsStride = 36;          // 32 pair sums per row + 4: rows 16-byte aligned, b128 reads conflict-free
 constexpr int kRsFloats = kRsGroup * kRsComp * kRsStride;
+// DEPTH (a depth gradient is present): a twelfth row, sum of weight * v_depth = d loss / d depth (tuple slot 11)
+constexpr int rs_comp(bool depth) { return depth ? kRsComp + 1 : kRsComp; }
+constexpr int rs_floats(bool depth) { return kRsGroup * rs_comp(depth) * kRsStride; }
 
-struct RsRecB { float x, y, cx, cy, cz, r, g, b, nmid, kmul, qx, qz, pvx, pvy; };
+struct RsRecB { float x, y, cx, cy, cz, r, g, b, nmid, kmul, qx, qz, pvx, pvy, d; };
 
+template <bool DEPTH>
 __device__ __forceinline__ RsRecB load_rs_b(const float* __restrict__ records, const float* __restrict__ pix_vel,
                                             unsigned gi, unsigned g) {
   const float* p = records + (size_t)gi * kRecFloats;
@@ -296,7 +300,16 @@ __device__ __forceinline__ RsRecB load_rs_b(const float* __restrict__ records, c
   o.x = p[0]; o.y = p[1]; o.cx = p[2]; o.cy = p[3]; o.cz = p[4]; o.r = p[6]; o.g = p[7]; o.b = p[8];
   o.nmid = p[kRecNmid]; o.kmul = p[kRecKmul]; o.qx = p[kRecQx]; o.qz = p[kRecQz];
   o.pvx = pix_vel[2 * (size_t)g]; o.pvy = pix_vel[2 * (size_t)g + 1];
+  o.d = DEPTH ? p[9] : 0.f;                          // the mid-exposure camera-space depth
   return o;
+}
+
+// w = v(lane) + v(lane ^ 1) for one value (the depth row; s_nop as in pair_sum11)
+__device__ __forceinline__ void rs_pair_sum1(float& v) {
+  asm volatile(
+      "s_nop 1\n\t"
+      "v_add_f32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf"
+      : "+v"(v));
 }
 
 // w[i] = v[i](lane) + v[i](lane ^ 1) for eleven values (see raster_bwd.hip pair_sum9 for the s_nop)
@@ -319,17 +332,19 @@ __device__ __forceinline__ void pair_sum11(float (&v)[11]) {
 }
 
 // pixel k of a lane lies in the 8x8 quadrant (k & 1, k >> 1) of the tile; its row decides tau: two values per lane
-struct RsQuad { float T[4], Dv[4], vr[4], vg[4], vb[4], py[4], tau[2]; int fin[4]; };
+// vd: the pixel's d loss / d depth (DEPTH only; the depth is a fourth colour channel with background 0, so it joins cv)
+struct RsQuad { float T[4], Dv[4], vr[4], vg[4], vb[4], py[4], tau[2], vd[4]; int fin[4]; };
 
 // One list entry against the lane's four pixels (returns whether any lane of the wave was hit; then the lane pair's 11
 // partial sums are in LDS rows slot*11 .. slot*11+10, column lane >> 1).  Slot 5 carries the plain sum of v_sigma (tuple
 // flag 2: the tuple reduce divides by -opacity once per Gaussian).
+template <bool DEPTH>
 __device__ __forceinline__ bool rs_bwd_entry(const RsRecB& rc, float pxf, int idx, RsQuad& pp, float* __restrict__ red,
                                              int slot, int lane, float agm) {
   const float dxa = rc.x - pxf, dxb = rc.x - (pxf + 8.0f);
   const float qy = rc.cy * kNegLog2e;
   float M00 = 0.f, M10 = 0.f, M01 = 0.f, M20 = 0.f, M11 = 0.f, M02 = 0.f, T10 = 0.f, T01 = 0.f;
-  float q_r = 0.f, q_g = 0.f, q_b = 0.f;
+  float q_r = 0.f, q_g = 0.f, q_b = 0.f, q_d = 0.f;
   bool any = false;
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
@@ -347,7 +362,8 @@ __device__ __forceinline__ bool rs_bwd_entry(const RsRecB& rc, float pxf, int id
     pp.T[k] *= ra;                                                    // transmittance in front of this entry
     const float fac = alpha * pp.T[k];
     q_r = fmaf(fac, pp.vr[k], q_r); q_g = fmaf(fac, pp.vg[k], q_g); q_b = fmaf(fac, pp.vb[k], q_b);
-    const float cv = fmaf(rc.b, pp.vb[k], fmaf(rc.g, pp.vg[k], rc.r * pp.vr[k]));
+    float cv = fmaf(rc.b, pp.vb[k], fmaf(rc.g, pp.vg[k], rc.r * pp.vr[k]));
+    if (DEPTH) { q_d = fmaf(fac, pp.vd[k], q_d); cv = fmaf(rc.d, pp.vd[k], cv); }
     const float v_al = fmaf(pp.T[k], cv, -(ra * pp.Dv[k]));
     pp.Dv[k] = fmaf(fac, cv, pp.Dv[k]);
     const float v_sigma = -ovm * v_al;
@@ -366,140 +382,155 @@ __device__ __forceinline__ bool rs_bwd_entry(const RsRecB& rc, float pxf, int id
   w[9] = fmaf(rc.cx, T10, rc.cy * T01);                               // d / d pixel velocity
   w[10] = fmaf(rc.cy, T10, rc.cz * T01);
   pair_sum11(w);
+  if (DEPTH) rs_pair_sum1(q_d);
   if ((lane & 1) == 0) {
-    float* r0 = red + slot * (kRsComp * kRsStride) + (lane >> 1);
+    float* r0 = red + slot * (rs_comp(DEPTH) * kRsStride) + (lane >> 1);
 #pragma unroll
     for (int c = 0; c < kRsComp; ++c) r0[c * kRsStride] = w[c];
+    if (DEPTH) r0[kRsComp * kRsStride] = q_d;
   }
   return true;
 }
 
-template <bool STATE>
-__global__ __launch_bounds__(256) void raster_bwd_rs_kernel(
-    RasterParams prm, RsParams rs, const int* __restrict__ ids, const int* __restrict__ eids,
-    const float* __restrict__ records, unsigned max_id, const float* __restrict__ out_T,
-    const int* __restrict__ final_idx, const float* __restrict__ v_img, const float* __restrict__ v_alpha,
-    unsigned n_blocks, float* __restrict__ bwd_T, float* __restrict__ bwd_B, float* __restrict__ tuples,
-    unsigned char* __restrict__ flags) {
-  __shared__ __attribute__((aligned(16))) float lds_all[4 * kRsFloats];
-  const int lane = lane_id();
-  float* red = lds_all + (threadIdx.x >> 6) * kRsFloats;
-  const int T = prm.tiles_x * prm.tiles_y;
-  const unsigned work = (unsigned)__builtin_amdgcn_readfirstlane(
-      (int)(xcd_remap(blockIdx.x, n_blocks) * 4u + (threadIdx.x >> 6)));
-  if (work >= (unsigned)(prm.S * T)) return;
-  const int s = work / T, t = work % T;
-  const int ty = t / prm.tiles_x, tx = t % prm.tiles_x;
-  const bool shared = rs.times != nullptr;
-  const float t_s = shared ? rs.times[s] : 0.f;
-  int2 range = prm.tile_bins[shared ? (size_t)t : (size_t)s * T + t];
-  range.x = __builtin_amdgcn_readfirstlane(range.x);
-  range.y = __builtin_amdgcn_readfirstlane(range.y);
-  if (range.y <= range.x) return;
-  // lane -> its four pixels, one per 8x8 quadrant: pixel k at (px0 + 8 (k & 1), py0 + 8 (k >> 1))
-  const int px0 = tx * K::kTile + (lane & 7);
-  const int py0 = ty * K::kTile + (lane >> 3);
-  const float pxf = (float)px0 + 0.5f;
-  const float bgr = prm.background[0], bgg = prm.background[1], bgb = prm.background[2];
-  RsQuad pp;
-  int my_end = range.x;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int x = px0 + 8 * (k & 1), y = py0 + 8 * (k >> 1);
-    float Tk = 1.f, Dv = 0.f, vr = 0.f, vg = 0.f, vb = 0.f;
-    int fin = range.x;
-    if (x < prm.W && y < prm.H) {
-      const size_t pix = ((size_t)s * prm.H + y) * prm.W + x;
-      const float Tfin = out_T[pix];
-      fin = min(max(final_idx[pix], range.x), range.y);      // a stop index never leaves the tile's list
-      vr = v_img[pix * 3 + 0]; vg = v_img[pix * 3 + 1]; vb = v_img[pix * 3 + 2];
-      if (prm.cmb_scale) {
-        const size_t q = ((size_t)y * prm.W + x) * 3;
-        vr = combine_grad(vr, prm.cmb_scale[q + 0], prm.cmb_gamma, prm.cmb_min);
-        vg = combine_grad(vg, prm.cmb_scale[q + 1], prm.cmb_gamma, prm.cmb_min);
-        vb = combine_grad(vb, prm.cmb_scale[q + 2], prm.cmb_gamma, prm.cmb_min);
-      }
-      const float va_out = v_alpha ? v_alpha[pix] : 0.f;
-      const float va = Tfin * (va_out - (bgr * vr + bgg * vg + bgb * vb));
-      Tk = Tfin;
-      Dv = -va;
-      if (STATE) { Tk = bwd_T[pix]; Dv = bwd_B[pix] - va; }
-    }
-    my_end = max(my_end, fin);
-    pp.T[k] = Tk; pp.Dv[k] = Dv; pp.vr[k] = vr; pp.vg[k] = vg; pp.vb[k] = vb; pp.py[k] = (float)y + 0.5f; pp.fin[k] = fin;
-  }
-  pp.tau[0] = rs_tau((float)py0 + 0.5f, (float)prm.H, rs.rs_time, t_s);
-  pp.tau[1] = rs_tau((float)(py0 + 8) + 0.5f, (float)prm.H, rs.rs_time, t_s);
-  const int wave_end = __builtin_amdgcn_readfirstlane(wave_max_i(my_end));
-  const float agm = prm.alpha_grad_max;
-  const unsigned s_base = shared ? 0u : (unsigned)s * (unsigned)rs.N;
-  const unsigned max_g = (unsigned)(rs.N - 1);
-  // shared list: the S samples' waves write the SAME entry's gradients — every (entry, sample) pair gets a tuple of its
-  // own, e * S + s (the S tuples of an entry are adjacent, a Gaussian's tuples stay one contiguous range)
-  const unsigned tmul = shared ? (unsigned)prm.S : 1u, tofs = shared ? (unsigned)s : 0u;
-  const unsigned n = (unsigned)(wave_end - range.x);
-  if (n != 0u) {
-    const int row = lane;                                    // row-sum role: lanes 0..43
-    const int row_g = row / kRsComp, row_c = row - row_g * kRsComp;
-    const int4* __restrict__ ids4 = reinterpret_cast<const int4*>(ids);
-    const int4* __restrict__ eids4 = reinterpret_cast<const int4*>(eids);
-    auto rec = [&](int id) {
-      const unsigned gi = min((unsigned)id, max_id);
-      return load_rs_b(records, rs.pix_vel, gi, min(gi - s_base, max_g));
-    };
-    int b = (wave_end - 1) & ~3;
-    const int b_last = range.x & ~3;
-    int4 idv = ids4[b >> 2];
-    RsRecB a0 = rec(idv.w), a1 = rec(idv.z);
-    for (;;) {
-      // pair A (entries b+3, b+2) is ready; put pair B (b+1, b) and the indices of the next (lower) group in flight
-      asm volatile("" :: "s"(a0.x), "s"(a1.x), "s"(a0.pvx), "s"(a1.pvx) : "memory");
-      const RsRecB b0 = rec(idv.y), b1 = rec(idv.x);
-      const int4 ev = eids4[b >> 2];
-      idv = ids4[max(b - 4, 0) >> 2];
-      asm volatile("" ::: "memory");
-      unsigned filled = 0;
-      if ((unsigned)(b + 3 - range.x) < n && rs_bwd_entry(a0, pxf, b + 3, pp, red, 3, lane, agm)) filled |= 8u;
-      if ((unsigned)(b + 2 - range.x) < n && rs_bwd_entry(a1, pxf, b + 2, pp, red, 2, lane, agm)) filled |= 4u;
-      asm volatile("" :: "s"(b0.x), "s"(b1.x), "s"(b0.pvx), "s"(b1.pvx), "s"(idv.x), "s"(ev.x) : "memory");
-      a0 = rec(idv.w); a1 = rec(idv.z);
-      asm volatile("" ::: "memory");
-      if ((unsigned)(b + 1 - range.x) < n && rs_bwd_entry(b0, pxf, b + 1, pp, red, 1, lane, agm)) filled |= 2u;
-      if ((unsigned)(b - range.x) < n && rs_bwd_entry(b1, pxf, b, pp, red, 0, lane, agm)) filled |= 1u;
-      if (filled) {
-        __builtin_amdgcn_wave_barrier();
-        if (row < kRsGroup * kRsComp && ((filled >> row_g) & 1u)) {
-          const f4* rp = reinterpret_cast<const f4*>(red + row * kRsStride);
-          f4 s0 = rp[0], s1 = rp[1], s2 = rp[2], s3 = rp[3];
-          s0 += rp[4]; s1 += rp[5]; s2 += rp[6]; s3 += rp[7];
-          const f4 v = (s0 + s1) + (s2 + s3);
-          const float sum = (v.x + v.y) + (v.z + v.w);
-          const int id_e = row_g == 0 ? ev.x : (row_g == 1 ? ev.y : (row_g == 2 ? ev.z : ev.w));
-          const size_t e = (size_t)(unsigned)id_e * tmul + tofs;
-          tuples[e * kGradFloats + row_c] = sum;
-          if (row_c == 0) flags[e] = 2;                      // 2: slot 5 is the plain sum of v_sigma
-        }
-        __builtin_amdgcn_wave_barrier();
-      }
-      if (b <= b_last) break;
-      b -= 4;
-    }
-  }
-  if (STATE) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int x = px0 + 8 * (k & 1), y = py0 + 8 * (k >> 1);
-      if (x < prm.W && y < prm.H) {
-        const size_t pix = ((size_t)s * prm.H + y) * prm.W + x;
-        const float Tfin = out_T[pix];
-        const float va_out = v_alpha ? v_alpha[pix] : 0.f;
-        const float va = Tfin * (va_out - (bgr * pp.vr[k] + bgg * pp.vg[k] + bgb * pp.vb[k]));
-        bwd_T[pix] = pp.T[k];
-        bwd_B[pix] = pp.Dv[k] + va;
-      }
-    }
-  }
+// raster_bwd_rs_kernel<STATE> and its depth-gradient twin raster_bwd_rs_depth_kernel<STATE> (v_depth [S,H,W] = d loss /
+// d depth_acc, a twelfth reduced row = tuple slot 11) are ONE source, instantiated by this macro with DEPTH = false /
+// true: the default kernels keep their names and instruction streams (a shared __device__ body changes the latter).
+#define GS_RS_NO_DEPTH_PARAM
+#define GS_RS_DEPTH_PARAM , const float* __restrict__ v_depth
+#define GS_BWD_RS_KERNEL(NAME, DEPTH, DEPTH_PARAM, PROLOGUE)                                                              \
+template <bool STATE>                                                                                                   \
+__global__ __launch_bounds__(256) void NAME(                                                                            \
+    RasterParams prm, RsParams rs, const int* __restrict__ ids, const int* __restrict__ eids,                           \
+    const float* __restrict__ records, unsigned max_id, const float* __restrict__ out_T,                                \
+    const int* __restrict__ final_idx, const float* __restrict__ v_img, const float* __restrict__ v_alpha,             \
+    unsigned n_blocks, float* __restrict__ bwd_T, float* __restrict__ bwd_B, float* __restrict__ tuples,              \
+    unsigned char* __restrict__ flags DEPTH_PARAM) {                                                                    \
+  PROLOGUE                                                                                                              \
+  __shared__ __attribute__((aligned(16))) float lds_all[4 * rs_floats(DEPTH)];                                         \
+  const int lane = lane_id();                                                                                               \
+  float* red = lds_all + (threadIdx.x >> 6) * rs_floats(DEPTH);                                                             \
+  const int T = prm.tiles_x * prm.tiles_y;                                                                                  \
+  const unsigned work = (unsigned)__builtin_amdgcn_readfirstlane(                                                           \
+      (int)(xcd_remap(blockIdx.x, n_blocks) * 4u + (threadIdx.x >> 6)));                                                    \
+  if (work >= (unsigned)(prm.S * T)) return;                                                                                \
+  const int s = work / T, t = work % T;                                                                                     \
+  const int ty = t / prm.tiles_x, tx = t % prm.tiles_x;                                                                     \
+  const bool shared = rs.times != nullptr;                                                                                  \
+  const float t_s = shared ? rs.times[s] : 0.f;                                                                             \
+  int2 range = prm.tile_bins[shared ? (size_t)t : (size_t)s * T + t];                                                       \
+  range.x = __builtin_amdgcn_readfirstlane(range.x);                                                                        \
+  range.y = __builtin_amdgcn_readfirstlane(range.y);                                                                        \
+  if (range.y <= range.x) return;                                                                                           \
+  /* lane -> its four pixels, one per 8x8 quadrant: pixel k at (px0 + 8 (k & 1), py0 + 8 (k >> 1)) */                       \
+  const int px0 = tx * K::kTile + (lane & 7);                                                                               \
+  const int py0 = ty * K::kTile + (lane >> 3);                                                                              \
+  const float pxf = (float)px0 + 0.5f;                                                                                      \
+  const float bgr = prm.background[0], bgg = prm.background[1], bgb = prm.background[2];                                    \
+  RsQuad pp;                                                                                                                \
+  int my_end = range.x;                                                                                                     \
+_Pragma("unroll")                                                                                                           \
+  for (int k = 0; k < 4; ++k) {                                                                                             \
+    const int x = px0 + 8 * (k & 1), y = py0 + 8 * (k >> 1);                                                                \
+    float Tk = 1.f, Dv = 0.f, vr = 0.f, vg = 0.f, vb = 0.f, vd = 0.f;                                                       \
+    int fin = range.x;                                                                                                      \
+    if (x < prm.W && y < prm.H) {                                                                                           \
+      const size_t pix = ((size_t)s * prm.H + y) * prm.W + x;                                                               \
+      const float Tfin = out_T[pix];                                                                                        \
+      fin = min(max(final_idx[pix], range.x), range.y);      /* a stop index never leaves the tile's list */                \
+      if (DEPTH) vd = v_depth[pix];                                                                                         \
+      vr = v_img[pix * 3 + 0]; vg = v_img[pix * 3 + 1]; vb = v_img[pix * 3 + 2];                                            \
+      if (prm.cmb_scale) {                                                                                                  \
+        const size_t q = ((size_t)y * prm.W + x) * 3;                                                                       \
+        vr = combine_grad(vr, prm.cmb_scale[q + 0], prm.cmb_gamma, prm.cmb_min);                                            \
+        vg = combine_grad(vg, prm.cmb_scale[q + 1], prm.cmb_gamma, prm.cmb_min);                                            \
+        vb = combine_grad(vb, prm.cmb_scale[q + 2], prm.cmb_gamma, prm.cmb_min);                                            \
+      }                                                                                                                     \
+      const float va_out = v_alpha ? v_alpha[pix] : 0.f;                                                                    \
+      const float va = Tfin * (va_out - (bgr * vr + bgg * vg + bgb * vb));                                                  \
+      Tk = Tfin;                                                                                                            \
+      Dv = -va;                                                                                                             \
+      if (STATE) { Tk = bwd_T[pix]; Dv = bwd_B[pix] - va; }                                                                 \
+    }                                                                                                                       \
+    my_end = max(my_end, fin);                                                                                              \
+    pp.T[k] = Tk; pp.Dv[k] = Dv; pp.vr[k] = vr; pp.vg[k] = vg; pp.vb[k] = vb; pp.py[k] = (float)y + 0.5f; pp.fin[k] = fin;  \
+    pp.vd[k] = vd;                                                                                                          \
+  }                                                                                                                         \
+  pp.tau[0] = rs_tau((float)py0 + 0.5f, (float)prm.H, rs.rs_time, t_s);                                                     \
+  pp.tau[1] = rs_tau((float)(py0 + 8) + 0.5f, (float)prm.H, rs.rs_time, t_s);                                               \
+  const int wave_end = __builtin_amdgcn_readfirstlane(wave_max_i(my_end));                                                  \
+  const float agm = prm.alpha_grad_max;                                                                                     \
+  const unsigned s_base = shared ? 0u : (unsigned)s * (unsigned)rs.N;                                                       \
+  const unsigned max_g = (unsigned)(rs.N - 1);                                                                              \
+  /* shared list: the S samples' waves write the SAME entry's gradients — every (entry, sample) pair gets a tuple of its */ \
+  /* own, e * S + s (the S tuples of an entry are adjacent, a Gaussian's tuples stay one contiguous range) */               \
+  const unsigned tmul = shared ? (unsigned)prm.S : 1u, tofs = shared ? (unsigned)s : 0u;                                    \
+  const unsigned n = (unsigned)(wave_end - range.x);                                                                        \
+  if (n != 0u) {                                                                                                            \
+    constexpr int kRows = rs_comp(DEPTH);                                                                                   \
+    const int row = lane;                                    /* row-sum role: lanes 0..43 (0..47 with DEPTH) */             \
+    const int row_g = row / kRows, row_c = row - row_g * kRows;   /* row_c = tuple slot (DEPTH: 11 = d loss / d depth) */   \
+    const int4* __restrict__ ids4 = reinterpret_cast<const int4*>(ids);                                                     \
+    const int4* __restrict__ eids4 = reinterpret_cast<const int4*>(eids);                                                   \
+    auto rec = [&](int id) {                                                                                                \
+      const unsigned gi = min((unsigned)id, max_id);                                                                        \
+      return load_rs_b<DEPTH>(records, rs.pix_vel, gi, min(gi - s_base, max_g));                                            \
+    };                                                                                                                      \
+    int b = (wave_end - 1) & ~3;                                                                                            \
+    const int b_last = range.x & ~3;                                                                                        \
+    int4 idv = ids4[b >> 2];                                                                                                \
+    RsRecB a0 = rec(idv.w), a1 = rec(idv.z);                                                                                \
+    for (;;) {                                                                                                              \
+      /* pair A (entries b+3, b+2) is ready; put pair B (b+1, b) and the indices of the next (lower) group in flight */     \
+      asm volatile("" :: "s"(a0.x), "s"(a1.x), "s"(a0.pvx), "s"(a1.pvx) : "memory");                                        \
+      const RsRecB b0 = rec(idv.y), b1 = rec(idv.x);                                                                        \
+      const int4 ev = eids4[b >> 2];                                                                                        \
+      idv = ids4[max(b - 4, 0) >> 2];                                                                                       \
+      asm volatile("" ::: "memory");                                                                                        \
+      unsigned filled = 0;                                                                                                  \
+      if ((unsigned)(b + 3 - range.x) < n && rs_bwd_entry<DEPTH>(a0, pxf, b + 3, pp, red, 3, lane, agm)) filled |= 8u;      \
+      if ((unsigned)(b + 2 - range.x) < n && rs_bwd_entry<DEPTH>(a1, pxf, b + 2, pp, red, 2, lane, agm)) filled |= 4u;      \
+      asm volatile("" :: "s"(b0.x), "s"(b1.x), "s"(b0.pvx), "s"(b1.pvx), "s"(idv.x), "s"(ev.x) : "memory");                 \
+      a0 = rec(idv.w); a1 = rec(idv.z);                                                                                     \
+      asm volatile("" ::: "memory");                                                                                        \
+      if ((unsigned)(b + 1 - range.x) < n && rs_bwd_entry<DEPTH>(b0, pxf, b + 1, pp, red, 1, lane, agm)) filled |= 2u;      \
+      if ((unsigned)(b - range.x) < n && rs_bwd_entry<DEPTH>(b1, pxf, b, pp, red, 0, lane, agm)) filled |= 1u;              \
+      if (filled) {                                                                                                         \
+        __builtin_amdgcn_wave_barrier();                                                                                    \
+        if (row < kRsGroup * kRows && ((filled >> row_g) & 1u)) {                                                           \
+          const f4* rp = reinterpret_cast<const f4*>(red + row * kRsStride);                                                \
+          f4 s0 = rp[0], s1 = rp[1], s2 = rp[2], s3 = rp[3];                                                                \
+          s0 += rp[4]; s1 += rp[5]; s2 += rp[6]; s3 += rp[7];                                                               \
+          const f4 v = (s0 + s1) + (s2 + s3);                                                                               \
+          const float sum = (v.x + v.y) + (v.z + v.w);                                                                      \
+          const int id_e = row_g == 0 ? ev.x : (row_g == 1 ? ev.y : (row_g == 2 ? ev.z : ev.w));                            \
+          const size_t e = (size_t)(unsigned)id_e * tmul + tofs;                                                            \
+          tuples[e * kGradFloats + row_c] = sum;                                                                            \
+          if (row_c == 0) flags[e] = 2;                      /* 2: slot 5 is the plain sum of v_sigma */                    \
+        }                                                                                                                   \
+        __builtin_amdgcn_wave_barrier();                                                                                    \
+      }                                                                                                                     \
+      if (b <= b_last) break;                                                                                               \
+      b -= 4;                                                                                                               \
+    }                                                                                                                       \
+  }                                                                                                                         \
+  if (STATE) {                                                                                                              \
+_Pragma("unroll")                                                                                                           \
+    for (int k = 0; k < 4; ++k) {                                                                                           \
+      const int x = px0 + 8 * (k & 1), y = py0 + 8 * (k >> 1);                                                              \
+      if (x < prm.W && y < prm.H) {                                                                                         \
+        const size_t pix = ((size_t)s * prm.H + y) * prm.W + x;                                                             \
+        const float Tfin = out_T[pix];                                                                                      \
+        const float va_out = v_alpha ? v_alpha[pix] : 0.f;                                                                  \
+        const float va = Tfin * (va_out - (bgr * pp.vr[k] + bgg * pp.vg[k] + bgb * pp.vb[k]));                              \
+        bwd_T[pix] = pp.T[k];                                                                                               \
+        bwd_B[pix] = pp.Dv[k] + va;                                                                                         \
+      }                                                                                                                     \
+    }                                                                                                                       \
+  }                                                                                                                         \
 }
+
+GS_BWD_RS_KERNEL(raster_bwd_rs_kernel, false, GS_RS_NO_DEPTH_PARAM, const float* const v_depth = nullptr; (void)v_depth;)
+GS_BWD_RS_KERNEL(raster_bwd_rs_depth_kernel, true, GS_RS_DEPTH_PARAM, )
 
 }  // namespace gs
 
@@ -532,14 +563,16 @@ GS_EXPORT int gs_rasterize_fwd_rs_slice(const float* records, const int* tile_bi
 // Backward of the same slice: tuples [I*12] (slots 0..8 as gs_rasterize_bwd_slice, 9..10 = d loss / d pixel velocity),
 // flags [I] zeroed by the caller — shared_list_times != NULL: tuples [I*S*12], flags [I*S], entry e / sample s at e*S+s; sorted_vals = emission index of every sorted entry; bwd_T / bwd_B as in
 // gs_rasterize_bwd_slice (both NULL for a one-slice frame); variant: + 256 = upstream alpha-clamp gradient.
-GS_EXPORT int gs_rasterize_bwd_rs_slice(const float* records, const int* sorted_vals, const int* tile_bins,
-                                        const int* band_edges, const float* background, int S, int H, int W,
-                                        const float* out_T, const int* final_idx, const float* v_img,
-                                        const float* v_alpha, float* bwd_T, float* bwd_B, float* tuples,
-                                        unsigned char* flags, const int* sorted_ids, int n_records, int variant,
-                                        const float* cmb_scale, float cmb_gamma, float cmb_min_level,
-                                        const float* pix_vel, int N, float rolling_shutter_time,
-                                        const float* shared_list_times, void* stream) {
+// gs_rasterize_bwd_rs_slice_depth (library-internal: csrc/frame.hip): v_depth [S,H,W] = d loss / d depth_acc, non-NULL
+// selects the depth specialisation (tuple slot 11 = d loss / d depth).
+extern "C" int gs_rasterize_bwd_rs_slice_depth(const float* records, const int* sorted_vals, const int* tile_bins,
+                                               const int* band_edges, const float* background, int S, int H, int W,
+                                               const float* out_T, const int* final_idx, const float* v_img,
+                                               const float* v_alpha, float* bwd_T, float* bwd_B, float* tuples,
+                                               unsigned char* flags, const int* sorted_ids, int n_records, int variant,
+                                               const float* cmb_scale, float cmb_gamma, float cmb_min_level,
+                                               const float* pix_vel, int N, float rolling_shutter_time,
+                                               const float* shared_list_times, const float* v_depth, void* stream) {
   if (S <= 0 || H <= 0 || W <= 0 || N <= 0 || !pix_vel || !sorted_ids || !tuples || !flags || n_records <= 0)
     return GS_ERR_INVALID;
   if ((bwd_T == nullptr) != (bwd_B == nullptr)) return GS_ERR_INVALID;
@@ -548,13 +581,35 @@ GS_EXPORT int gs_rasterize_bwd_rs_slice(const float* records, const int* sorted_
   if (variant & 256) prm.alpha_grad_max = 3.0e38f;
   RsParams rs; rs.pix_vel = pix_vel; rs.N = N; rs.rs_time = rolling_shutter_time; rs.times = shared_list_times;
   const unsigned work = (unsigned)(S * prm.tiles_x * prm.tiles_y), blocks = (work + 3) / 4;
-  if (bwd_T)
-    hipLaunchKernelGGL(raster_bwd_rs_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, prm, rs, sorted_ids,
-                       sorted_vals, records, (unsigned)(n_records - 1), out_T, final_idx, v_img, v_alpha, blocks, bwd_T,
-                       bwd_B, tuples, flags);
+  if (v_depth && bwd_T)
+    hipLaunchKernelGGL((raster_bwd_rs_depth_kernel<true>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, prm, rs,
+                       sorted_ids, sorted_vals, records, (unsigned)(n_records - 1), out_T, final_idx, v_img, v_alpha,
+                       blocks, bwd_T, bwd_B, tuples, flags, v_depth);
+  else if (v_depth)
+    hipLaunchKernelGGL((raster_bwd_rs_depth_kernel<false>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, prm, rs,
+                       sorted_ids, sorted_vals, records, (unsigned)(n_records - 1), out_T, final_idx, v_img, v_alpha,
+                       blocks, (float*)nullptr, (float*)nullptr, tuples, flags, v_depth);
+  else if (bwd_T)
+    hipLaunchKernelGGL(raster_bwd_rs_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, prm, rs,
+                       sorted_ids, sorted_vals, records, (unsigned)(n_records - 1), out_T, final_idx, v_img, v_alpha,
+                       blocks, bwd_T, bwd_B, tuples, flags);
   else
-    hipLaunchKernelGGL(raster_bwd_rs_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, prm, rs, sorted_ids,
-                       sorted_vals, records, (unsigned)(n_records - 1), out_T, final_idx, v_img, v_alpha, blocks,
-                       (float*)nullptr, (float*)nullptr, tuples, flags);
+    hipLaunchKernelGGL(raster_bwd_rs_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, prm, rs,
+                       sorted_ids, sorted_vals, records, (unsigned)(n_records - 1), out_T, final_idx, v_img, v_alpha,
+                       blocks, (float*)nullptr, (float*)nullptr, tuples, flags);
   return gs_launch_status();
+}
+
+GS_EXPORT int gs_rasterize_bwd_rs_slice(const float* records, const int* sorted_vals, const int* tile_bins,
+                                        const int* band_edges, const float* background, int S, int H, int W,
+                                        const float* out_T, const int* final_idx, const float* v_img,
+                                        const float* v_alpha, float* bwd_T, float* bwd_B, float* tuples,
+                                        unsigned char* flags, const int* sorted_ids, int n_records, int variant,
+                                        const float* cmb_scale, float cmb_gamma, float cmb_min_level,
+                                        const float* pix_vel, int N, float rolling_shutter_time,
+                                        const float* shared_list_times, void* stream) {
+  return gs_rasterize_bwd_rs_slice_depth(records, sorted_vals, tile_bins, band_edges, background, S, H, W, out_T,
+                                         final_idx, v_img, v_alpha, bwd_T, bwd_B, tuples, flags, sorted_ids, n_records,
+                                         variant, cmb_scale, cmb_gamma, cmb_min_level, pix_vel, N, rolling_shutter_time,
+                                         shared_list_times, nullptr, stream);
 }

@@ -5,7 +5,8 @@
               applied_transform, k3 (/root/reference/combine.py:118,127)
   per frame   file_path transform_matrix[4][4] camera_linear_velocity[3] camera_angular_velocity[3]
               (/root/reference/process_synthetic_inputs.py:171-176), optional motion_blur_score
-              (/root/reference/combine.py:79-81)
+              (/root/reference/combine.py:79-81); optional depth_file_path (nerfstudio's depth supervision field;
+              top-level depth_unit_scale_factor, default 1e-3: stored value * factor = scene units; load_depth)
   conventions camera-to-world in OpenGL axes; velocities in that camera frame
               (/root/reference/process_synthetic_inputs.py:157-165)
   eval split  "interval": sorted index i % 8 == 0 (/root/reference/train.py:174-177,
@@ -39,6 +40,9 @@ class TransformsScene:
     distortion: Dict[str, float] = field(default_factory=dict)
     ply_file_path: Optional[str] = None
     applied_transform: Optional[torch.Tensor] = None
+    # per frame: the depth map's path (nerfstudio's depth_file_path) or None; [] for scenes built by hand
+    depth_paths: List[Optional[str]] = field(default_factory=list)
+    depth_unit_scale_factor: float = 1e-3
 
 
 def split_indices(file_paths: List[str], eval_mode: str = "interval", eval_interval: int = 8) -> Tuple[List[int], List[int]]:
@@ -73,7 +77,7 @@ def load_transforms(path: str, eval_mode: str = "interval", eval_interval: int =
     readout = float(meta.get("rolling_shutter_time", 0.0))
     s = 1.0 / float(downscale)
     W, H = int(round(meta["w"] * s)), int(round(meta["h"] * s))
-    cams, paths = [], []
+    cams, paths, dpaths = [], [], []
     is_eval_set = set()
     tr, ev = split_indices([fr["file_path"] for fr in frames], eval_mode, eval_interval)
     is_eval_set.update(ev)
@@ -94,6 +98,8 @@ def load_transforms(path: str, eval_mode: str = "interval", eval_interval: int =
         cams.append(Camera(c2w[:3], float(fr.get("fl_x", meta["fl_x"])) * s, float(fr.get("fl_y", meta["fl_y"])) * s,
                            float(fr.get("cx", meta["cx"])) * s, float(fr.get("cy", meta["cy"])) * s, W, H, md))
         paths.append(os.path.normpath(os.path.join(root, fr["file_path"])))
+        dp = fr.get("depth_file_path")
+        dpaths.append(os.path.normpath(os.path.join(root, dp)) if dp else None)
     at = meta.get("applied_transform")
     return TransformsScene(
         cameras=cams, image_paths=paths, train_indices=tr, eval_indices=ev, exposure_time=exposure,
@@ -101,6 +107,7 @@ def load_transforms(path: str, eval_mode: str = "interval", eval_interval: int =
         distortion={k: float(meta[k]) for k in ("k1", "k2", "k3", "p1", "p2") if k in meta},
         ply_file_path=(os.path.normpath(os.path.join(root, meta["ply_file_path"])) if "ply_file_path" in meta else None),
         applied_transform=(torch.tensor(at, dtype=torch.float32) if at is not None else None),
+        depth_paths=dpaths, depth_unit_scale_factor=float(meta.get("depth_unit_scale_factor", 1e-3)),
     )
 
 
@@ -204,6 +211,70 @@ def load_scene_images(scene: "TransformsScene", device="cpu", undistort: bool = 
             x0, y0, x1, y1 = cam.metadata["undistort_roi"]
             img = img[y0:y1, x0:x1].contiguous()
         out.append(img)
+    return out
+
+
+def load_depth(path: str, scale: float = 1e-3, device="cpu") -> torch.Tensor:
+    """[H,W,1] float32 depth in scene units = stored value * scale (nerfstudio's depth_unit_scale_factor: 1e-3 turns
+    millimetres into metres), 0 = no measurement (so are non-finite and negative values).  `.npy` (any numeric
+    [H,W] or [H,W,1] array) or a single-channel image PIL decodes (16-bit PNG: mode I;16 / I)."""
+    import numpy as np
+    if path.endswith(".npy"):
+        arr = np.load(path)
+    else:
+        from PIL import Image
+        with Image.open(path) as im:
+            arr = np.asarray(im)
+    arr = np.asarray(arr, dtype=np.float64)
+    if arr.ndim == 3:
+        arr = arr[..., 0]
+    if arr.ndim != 2:
+        raise ValueError(f"{path}: a depth map must be [H,W] or [H,W,1], got shape {arr.shape}")
+    d = arr * float(scale)
+    d[~np.isfinite(d) | (d < 0)] = 0.0
+    return torch.from_numpy(d.astype(np.float32))[..., None].to(device)
+
+
+def undistort_depth(depth: torch.Tensor, fx: float, fy: float, cx: float, cy: float, distortion: Dict[str, float],
+                    crop: bool = False):
+    """undistort_image for a depth map [H,W,1] with NEAREST-neighbour sampling (an interpolated depth across an edge or
+    next to a missing measurement would be a depth nobody measured): pixels that look outside the source, or whose
+    nearest source pixel holds no measurement, are 0.  crop=True: cut to the same undistort_roi as the images."""
+    H, W = depth.shape[0], depth.shape[1]
+    if not _has_distortion(distortion):
+        return (depth, (0, 0, W, H)) if crop else depth
+    us, vs = _undistort_grid(H, W, fx, fy, cx, cy, distortion, depth.device)
+    ui, vi = torch.round(us).long(), torch.round(vs).long()
+    inside = (ui >= 0) & (ui < W) & (vi >= 0) & (vi < H)
+    src = depth[..., 0]
+    out = torch.where(inside, src[vi.clamp(0, H - 1), ui.clamp(0, W - 1)], torch.zeros((), dtype=depth.dtype))[..., None]
+    out = out.to(depth.dtype).contiguous()
+    if not crop:
+        return out
+    x0, y0, x1, y1 = undistort_roi(H, W, fx, fy, cx, cy, distortion)
+    return out[y0:y1, x0:x1].contiguous(), (x0, y0, x1, y1)
+
+
+def load_scene_depths(scene: "TransformsScene", device="cpu", undistort: bool = True) -> List[Optional[torch.Tensor]]:
+    """every frame's depth map [H,W,1] (load_depth with the scene's depth_unit_scale_factor), or None for a frame
+    without one — undistorted (nearest neighbour) and cropped exactly like load_scene_images' frames, whether or not
+    that call has already replaced scene.cameras by the cropped cameras."""
+    out: List[Optional[torch.Tensor]] = []
+    lens = undistort and _has_distortion(scene.distortion)
+    paths = scene.depth_paths or [None] * len(scene.cameras)
+    for cam, path in zip(scene.cameras, paths):
+        if path is None:
+            out.append(None)
+            continue
+        d = load_depth(path, scene.depth_unit_scale_factor, device)
+        if cam.metadata.get("undistorted", False):
+            # the camera describes the cropped frame: undistort with the full frame's principal point, same rectangle
+            x0, y0, x1, y1 = cam.metadata["undistort_roi"]
+            full = undistort_depth(d, cam.fx, cam.fy, cam.cx + x0, cam.cy + y0, scene.distortion) if lens else d
+            d = full[y0:y1, x0:x1].contiguous()
+        elif lens:
+            d, _ = undistort_depth(d, cam.fx, cam.fy, cam.cx, cam.cy, scene.distortion, crop=True)
+        out.append(d)
     return out
 
 

@@ -106,6 +106,17 @@ def _so3_exp(w: Tensor) -> Tensor:
     return eye + A * K + B * (K @ K)
 
 
+def expected_depth(depth_acc: Tensor, alphas: Tensor) -> Tensor:
+    """splatfacto's outputs["depth"] from the compositor's per-sample depth sums depth_acc [S,H,W] (sum of weight *
+    camera-space depth) and alphas [S,H,W]: d / a with d, a their means over the samples, [H,W,1].  Differentiable in d
+    and a; zero-alpha pixels hold far = d.max(), detached — splatfacto 1.1.0 fills them with depth_im.detach().max(), the
+    UN-normalised accumulated maximum (what render_model.py:219's colour maps are normalised against)."""
+    d = depth_acc.mean(dim=0)[..., None]
+    a = alphas.mean(dim=0)[..., None]
+    far = d.detach().max()
+    return torch.where(a > 0, d / torch.clamp(a, min=1e-10), far)
+
+
 class SplatfactoDeblurModel(nn.Module):
     """Gaussian parameters + ``get_outputs`` through the fused HIP path."""
 
@@ -286,10 +297,13 @@ class SplatfactoDeblurModel(nn.Module):
         return float(camera.metadata.get("rolling_shutter_time", 0.0))
 
     # -- rendering ---------------------------------------------------------------------
-    def get_outputs(self, camera: Camera, detach_gaussians: bool = False) -> Dict[str, Tensor]:
+    def get_outputs(self, camera: Camera, detach_gaussians: bool = False,
+                    return_depth: Optional[bool] = None) -> Dict[str, Tensor]:
         """detach_gaussians=True renders with the Gaussians as constants: only the camera-side parameters (pose /
         velocity adjustment, background) receive a gradient — what the fork's `--optimize-eval-cameras`
-        (/root/reference/train.py:180-183, README.md:197) needs for the evaluation frames."""
+        (/root/reference/train.py:180-183, README.md:197) needs for the evaluation frames.
+        out["depth"] (rendered with output_depth_during_training, in eval, or with return_depth=True) is differentiable
+        in training: a depth loss reaches the Gaussians and the camera adjustments (expected_depth)."""
         cfg = self.config
         dev = self.means.device
         d = self.downscale_factor()
@@ -317,7 +331,7 @@ class SplatfactoDeblurModel(nn.Module):
         gamma = cfg.gamma if use_gamma else 1.0
         min_level = cfg.min_rgb_level if use_gamma else 0.0
         # one autograd node for composite + gamma-space average: no [S,H,W,3] sample-gradient tensor in backward
-        want_depth = cfg.output_depth_during_training or not self.training
+        want_depth = (cfg.output_depth_during_training or not self.training) if return_depth is None else bool(return_depth)
         res = ops.render_combined(
             means_, scales_, quats_, opac_.reshape(-1), dc_,
             viewmats, bg, S, R, camera.fx, camera.fy, camera.cx, camera.cy, camera.height, camera.width,
@@ -335,25 +349,22 @@ class SplatfactoDeblurModel(nn.Module):
         out = {"rgb": torch.clamp(rgb, max=1.0),      # splatfacto clamps in training too
                "accumulation": accumulation, "background": bg}
         if depth_acc is not None:
-            # expected depth of the blended splats, from the SAME depth-sliced pass as the colour (a fourth
-            # forward-only channel of the compositor): mean over the samples of sum(weight * depth), over alpha
-            d = depth_acc.mean(dim=0)[..., None].detach()
-            a = accumulation.detach()
-            # zero-alpha pixels: splatfacto 1.1.0 fills with depth_im.detach().max(), the UN-normalised accumulated
-            # maximum (what render_model.py:219's colour maps are normalised against)
-            far = d.max()
-            out["depth"] = torch.where(a > 0, d / torch.clamp(a, min=1e-10), far)
+            out["depth"] = expected_depth(depth_acc, alphas)
         else:
             out["depth"] = None
         return out
 
-    def render_and_backward(self, camera: Camera, grad_image) -> Tensor:
+    def render_and_backward(self, camera: Camera, grad_image, grad_depth=None) -> Tensor:
         """One TRAINING frame, forward and backward in one host call (step.render_step: the same C-ABI calls as
         get_outputs + Tensor.backward, without the autograd engine between the two compositors — the entry bench.py
         times).  grad_image: callable rgb [H,W,3] -> d loss / d rgb, where rgb is what get_outputs()["rgb"] would hold
         (clamped at 1).  Gradients ACCUMULATE into .grad of the Gaussian parameters; pose / velocity adjustments and a
         learnable background get theirs through the small torch graph of _viewmat_and_velocity / _background.
-        Returns rgb (detached).  Same values as the autograd route (tests: test_train_step_routes_agree)."""
+        Returns rgb (detached).  Same values as the autograd route (tests: test_train_step_routes_agree).
+        grad_depth (optional): callable (depth [H,W,1], accumulation [H,W,1]) -> d loss / d depth [H,W,1], where depth is
+        what get_outputs()["depth"] would hold (expected_depth); its chain to the per-sample depth sums and alphas runs
+        here, and the frame's backward takes the depth term (step.render_step grad_depth).  None: rgb and every gradient
+        exactly as without it."""
         from .step import render_step
         cfg = self.config
         dev = self.means.device
@@ -378,6 +389,16 @@ class SplatfactoDeblurModel(nn.Module):
             v = grad_image(torch.clamp(rgb, max=1.0))
             return v * (rgb <= 1.0)
 
+        v_depth = None
+        if grad_depth is not None:
+            def v_depth(depth_acc, alphas):
+                da, al = depth_acc.requires_grad_(True), alphas.requires_grad_(True)
+                depth = expected_depth(da, al)
+                v = grad_depth(depth.detach(), al.detach().mean(dim=0)[..., None])
+                if v is None:
+                    raise ValueError("grad_depth(depth, accumulation) returned None: it must return d loss / d depth")
+                return torch.autograd.grad(depth, (da, al), v.detach().reshape(depth.shape), allow_unused=True)
+
         rgb, g, radii = render_step(
             self.means, self.scales, self.quats, self.opacities.reshape(-1), self.features_dc, viewmat.detach(),
             lin.detach(), ang.detach(), list(times) if shared else self._const(times), bg.detach(), S, R,
@@ -386,7 +407,8 @@ class SplatfactoDeblurModel(nn.Module):
             sh_degree=self.active_sh_degree(), antialiased=(cfg.rasterize_mode == "antialiased"),
             sh_rest=self.features_rest, raw_params=True, motion_model=cfg.motion_model, xy_grad_out=self.xy_grad,
             camera_grads=bool(cam_leaves), background_grad=bg.requires_grad,
-            rolling_shutter_time=self._rs_time(camera) if pixvel else 0.0, shared_list=shared, hints=self._hints_of(camera))
+            rolling_shutter_time=self._rs_time(camera) if pixvel else 0.0, shared_list=shared, hints=self._hints_of(camera),
+            grad_depth=v_depth)
         for p, gr in ((self.means, g["means"]), (self.scales, g["scales"]), (self.quats, g["quats"]),
                       (self.opacities, g["opacities"]), (self.features_dc, g["sh"]), (self.features_rest, g["sh_rest"])):
             gr = gr.view_as(p)

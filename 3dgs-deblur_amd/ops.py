@@ -814,14 +814,18 @@ def native_frame_forward(records: Tensor, depth_keys: Tensor, num_tiles_hit: Ten
 
 
 def native_frame_backward(frame, records: Tensor, bg: Tensor, edges: Tensor, out_T: Tensor, v_img: Tensor,
-                          v_alpha: Optional[Tensor], v_records: Tensor, touched: Tensor, combine=None):
+                          v_alpha: Optional[Tensor], v_records: Tensor, touched: Tensor, combine=None,
+                          v_depth: Optional[Tensor] = None):
+    """v_depth [S,H,W] (optional): d loss / d depth_acc — gs_frame_backward_depth leaves d loss / d record depth in
+    v_records[:, 11]; None issues gs_frame_backward, launch for launch what it always did"""
     L = _L()
     cmb = combine if combine is not None else (None, 1.0, 0.0)
     arena, state = frame["arena"], frame["state"]
     lease = frame["lease"]
     relent = lease.arena is None and _arena_relend(frame)
     try:
-        _native_frame_backward(L, frame, arena, state, records, bg, edges, out_T, v_img, v_alpha, v_records, touched, cmb)
+        _native_frame_backward(L, frame, arena, state, records, bg, edges, out_T, v_img, v_alpha, v_records, touched, cmb,
+                               v_depth)
     finally:
         if relent:
             _arena_return(frame)
@@ -831,12 +835,20 @@ def native_frame_backward(frame, records: Tensor, bg: Tensor, edges: Tensor, out
             lease.release()
 
 
-def _native_frame_backward(L, frame, arena, state, records, bg, edges, out_T, v_img, v_alpha, v_records, touched, cmb):
+def _native_frame_backward(L, frame, arena, state, records, bg, edges, out_T, v_img, v_alpha, v_records, touched, cmb,
+                           v_depth=None):
     L.gs_frame_profile_enable(_profile_mask())
-    st = L.gs_frame_backward(ctypes.byref(state), _ptr(records), _ptr(bg), _ptr(edges), _ptr(out_T), _ptr(v_img),
-                             _ptr(v_alpha), _ptr(cmb[0]), float(cmb[1]), float(cmb[2]), _bwd_variant(), _ptr(v_records),
-                             _ptr(touched), _ptr(frame.get("pix_vel")), _ptr(frame.get("sample_times")), _ptr(arena),
-                             arena.numel(), _stream())
+    if v_depth is None:
+        st = L.gs_frame_backward(ctypes.byref(state), _ptr(records), _ptr(bg), _ptr(edges), _ptr(out_T), _ptr(v_img),
+                                 _ptr(v_alpha), _ptr(cmb[0]), float(cmb[1]), float(cmb[2]), _bwd_variant(), _ptr(v_records),
+                                 _ptr(touched), _ptr(frame.get("pix_vel")), _ptr(frame.get("sample_times")), _ptr(arena),
+                                 arena.numel(), _stream())
+    else:
+        st = L.gs_frame_backward_depth(ctypes.byref(state), _ptr(records), _ptr(bg), _ptr(edges), _ptr(out_T),
+                                       _ptr(v_img), _ptr(v_alpha), _ptr(cmb[0]), float(cmb[1]), float(cmb[2]),
+                                       _bwd_variant(), _ptr(v_records), _ptr(touched), _ptr(frame.get("pix_vel")),
+                                       _ptr(frame.get("sample_times")), _ptr(arena), arena.numel(), _ptr(v_depth),
+                                       _stream())
     if st == 3:
         raise _lib.HipLibraryError("frame_backward: the forward's arena cannot hold the backward's buffers "
                                    "(call native_frame_forward with reserve_backward=True)")
@@ -1286,7 +1298,8 @@ class _RenderSubposes(Function):
         # deferred colour: the view direction of every sub-pose (pixel-velocity model: the mid-exposure pose for all)
         V_col = V.reshape(1, 16).expand(P, 16).contiguous() if pixvel else V
         color = (means3d, sh, sh_rest, K, args[4], V_col) if (defer_flags & 1) else None
-        # optional fourth channel: sum of weight * camera-space depth per sample image (forward only)
+        # optional fourth channel: sum of weight * camera-space depth per sample image (differentiable: the backward's
+        # depth specialisations, gs_frame_backward_depth)
         depth_acc = torch.zeros(S, H, W, device=dev) if return_depth else None
         ctx.prealloc = None
         ctx.frame = None
@@ -1363,21 +1376,25 @@ class _RenderSubposes(Function):
         ctx.n_isect = n_isect
         ctx.bg_grad = background is not None and ctx.needs_input_grad[6]
         ctx.mark_non_differentiable(radii)
-        if depth_acc is not None:
-            ctx.mark_non_differentiable(depth_acc)
         ctx.img_shape = (S, H, W, 3) if gamma is None else (H, W, 3)
         return first, (1.0 - out_T) if return_alpha else None, radii, depth_acc
 
     @staticmethod
-    def backward(ctx, v_img, v_alpha, _v_radii, _v_depth=None):
+    def backward(ctx, v_img, v_alpha, _v_radii, v_depth=None):
         (means3d, scales, quats, opacities, sh, V, records, svals, bins, edges, bg, out_T, fidx, cmb_samples,
          cmb_rgb) = ctx.saved_tensors
         N, P, glob, K, deg, fx, fy, cx, cy, H, W, clip, aa = ctx.args
         S, R = ctx.SR
         dev = means3d.device
         L = _L()
-        if v_img is None and v_alpha is None:
+        if v_img is None and v_alpha is None and v_depth is None:
             return (None,) * 32
+        if v_depth is not None:
+            # d loss / d depth_acc [S,H,W]: the depth specialisations of the native frame backward (grad flag 64 below)
+            if ctx.frame is None:
+                raise NotImplementedError("a depth gradient needs the native frame backward (gs_frame_backward_depth); "
+                                          "the frame backend in use has no depth channel")
+            v_depth = v_depth.contiguous().float()
         v_img = torch.zeros(ctx.img_shape, device=dev) if v_img is None else v_img.contiguous().float()
         v_al = None if v_alpha is None else v_alpha.contiguous().float()
         combine = None
@@ -1412,7 +1429,7 @@ class _RenderSubposes(Function):
             touched = None
 
         if ctx.frame is not None:
-            native_frame_backward(ctx.frame, records, bg, edges, out_T, v_img, v_al, v_records, touched, combine)
+            native_frame_backward(ctx.frame, records, bg, edges, out_T, v_img, v_al, v_records, touched, combine, v_depth)
         else:
             ctx.backend.sliced_backward(records, ctx.slices, S, R, H, W, bg, edges, out_T, v_img, v_al, v_records, touched,
                                         combine, ctx.rs)
@@ -1427,7 +1444,7 @@ class _RenderSubposes(Function):
         v_sh_rest = outs[5] if sh_rest is not None else None
         need_v = ctx.needs_input_grad[5]
         xy_out = ctx.xy_grad_out
-        fill_flag = 32 if touched is not None else 0
+        fill_flag = (32 if touched is not None else 0) | (64 if v_depth is not None else 0)     # 64: v_records[:, 11]
         pf = ctx.param_flags
         v_lin = v_ang = None
         # scratch of the ordered camera-gradient reduction (the sparse form runs when touched flags exist)
@@ -1484,7 +1501,10 @@ def render_subposes(means3d: Tensor, scales: Tensor, quats: Tensor, opacities: T
     lin_vel / ang_vel [3] (OpenCV camera frame) and ONE mid-exposure viewmat [4,4] as `viewmats`; every Gaussian is
     projected once and sub-pose p renders it at xy + times[p] * pixel_velocity (gradients reach viewmat and twist).
     return_depth=True appends a 4th result [S,H,W]: per sample the sum over the blended splats of weight *
-    camera-space depth (no gradient); expected depth = that / alpha (splatfacto's outputs["depth"]).
+    camera-space depth; expected depth = that / alpha (splatfacto's outputs["depth"]).  It is differentiable with the
+    same weights as the colour, through the weights and through the depths: a Gaussian's depth under sub-pose p (SE(3)
+    sub-poses: gradients reach means and the sub-pose viewmats, hence viewmat and both velocities through
+    subpose_viewmats) or its mid-exposure depth (pixel-velocity model: means and viewmat, no twist term).
     rolling_shutter_time != 0 (pixel-velocity model, rs_bands == 1, times = the S blur-sample times): EXACT per-row
     rolling shutter — pixel row y sees every splat at xy + (times[s] + tau(y)) * pixel_velocity with
     tau(y) = ((y + 0.5) / H - 0.5) * rolling_shutter_time; one projection / sort / list per blur sample, whatever H.

@@ -45,14 +45,20 @@ def render_step(means: Tensor, scales: Tensor, quats: Tensor, opacities: Tensor,
                 sh_degree: int = 3, antialiased: bool = True, sh_rest: Optional[Tensor] = None, raw_params: bool = True,
                 motion_model: str = "se3", xy_grad_out: Optional[Tensor] = None, camera_grads: bool = True,
                 background_grad: bool = False, glob_scale: float = 1.0, clip_thresh: float = 0.01,
-                rolling_shutter_time: float = 0.0, shared_list: bool = False, hints: Optional["ops.FrameHints"] = None
+                rolling_shutter_time: float = 0.0, shared_list: bool = False, hints: Optional["ops.FrameHints"] = None,
+                grad_depth: Optional[Union[Tensor, Callable[[Tensor, Tensor], Tuple[Tensor, Optional[Tensor]]]]] = None
                 ) -> Tuple[Tensor, Dict[str, Optional[Tensor]], Tensor]:
     """One frame, forward and backward.  Arguments as ops.render_combined (raw_params: log-scales / opacity logits;
     sh_rest: features_rest beside sh = features_dc), but the camera comes as ONE mid-exposure `viewmat` [4,4] + body
     twist + the P sub-pose `times` for both motion models.  grad_image: d loss / d rgb [H,W,3], or a callable
     rgb -> d loss / d rgb that is invoked between the two halves.
     -> (rgb [H,W,3], gradients {means, scales, quats, opacities, sh, sh_rest, viewmat, lin_vel, ang_vel, background},
-        radii [P,N] ([1,N] with shared_list, see ops.render_subposes)) — gradients of exactly the tensors handed in (raw parameters with raw_params=True)."""
+        radii [P,N] ([1,N] with shared_list, see ops.render_subposes)) — gradients of exactly the tensors handed in (raw parameters with raw_params=True).
+    grad_depth (optional; None: the step is unchanged, launch for launch): a depth loss on the per-sample depth sums
+    depth_acc [S,H,W] (sum over the blended splats of weight * camera-space depth, ops.render_subposes return_depth).
+    Either d loss / d depth_acc [S,H,W] as a tensor, or a callable (depth_acc [S,H,W], alphas [S,H,W]) ->
+    (d loss / d depth_acc, d loss / d alphas or None), invoked between the two halves like grad_image — a loss on the
+    expected depth depth_acc / alpha needs the alpha term (SplatfactoDeblurModel.render_and_backward does that chain)."""
     S, R = max(1, int(blur_samples)), max(1, int(rs_bands))
     pixvel = motion_model == "pixel_velocity"
     if not pixvel and motion_model != "se3":
@@ -66,10 +72,11 @@ def render_step(means: Tensor, scales: Tensor, quats: Tensor, opacities: Tensor,
     needs = [True, True, True, True, True, camera_grads, background is not None and background_grad] + [False] * 16 + \
             [camera_grads and pixvel, camera_grads and pixvel, False, False, False, sh_rest is not None, False, False]
     ctx = _Ctx(needs)
-    rgb, _alpha, radii, _depth = ops._RenderSubposes.forward(
+    depth = grad_depth is not None
+    rgb, alphas, radii, depth_acc = ops._RenderSubposes.forward(
         ctx, means, scales, quats, opacities, sh, vms, background, S, R, fx, fy, cx, cy, img_height, img_width,
-        sh_degree, antialiased, glob_scale, clip_thresh, xy_grad_out, False, float(gamma), float(min_rgb_level),
-        lin_vel if pixvel else None, ang_vel if pixvel else None, times if pixvel else None, False,
+        sh_degree, antialiased, glob_scale, clip_thresh, xy_grad_out, depth, float(gamma), float(min_rgb_level),
+        lin_vel if pixvel else None, ang_vel if pixvel else None, times if pixvel else None, depth,
         float(rolling_shutter_time), sh_rest, 3 if raw_params else 0, bool(shared_list), hints)
     if callable(grad_image):
         # the callable may use torch.autograd itself (rgb.requires_grad_() + autograd.grad): it sees a detached leaf and
@@ -81,7 +88,20 @@ def render_step(means: Tensor, scales: Tensor, quats: Tensor, opacities: Tensor,
         v_rgb = v_rgb.detach()
     else:
         v_rgb = grad_image
-    g = ops._RenderSubposes.backward(ctx, v_rgb, None, None, None)
+    v_alpha = v_depth = None
+    if callable(grad_depth):
+        with torch.enable_grad():
+            res = grad_depth(depth_acc.detach(), alphas.detach())
+        if not isinstance(res, (tuple, list)) or len(res) != 2 or res[0] is None:
+            raise ValueError("grad_depth(depth_acc, alphas) must return (d loss / d depth_acc [S,H,W], "
+                             "d loss / d alphas [S,H,W] or None)")
+        v_depth = res[0].detach()
+        v_alpha = None if res[1] is None else res[1].detach()
+    elif grad_depth is not None:
+        v_depth = grad_depth
+    if v_depth is not None and tuple(v_depth.shape) != (S, img_height, img_width):
+        raise ValueError(f"d loss / d depth_acc must be [S,H,W] = {(S, img_height, img_width)}, got {tuple(v_depth.shape)}")
+    g = ops._RenderSubposes.backward(ctx, v_rgb, v_alpha, None, v_depth)
     grads = {"means": g[0], "scales": g[1], "quats": g[2], "opacities": g[3], "sh": g[4], "background": g[6],
              "sh_rest": g[28], "viewmat": None, "lin_vel": None, "ang_vel": None}
     if pixvel:

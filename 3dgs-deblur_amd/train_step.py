@@ -74,6 +74,26 @@ def downscale_image(img: Tensor, d: int) -> Tensor:
     return F.avg_pool2d(img.permute(2, 0, 1)[None], kernel_size=d, stride=d)[0].permute(1, 2, 0).contiguous()
 
 
+def downscale_depth(depth: Tensor, d: int) -> Tensor:
+    """[H,W,1] depth map (0 = no measurement) -> [H//d, W//d, 1]: per d x d block the mean of its VALID samples, 0 where
+    the block holds none (the depth counterpart of downscale_image: an invalid pixel never drags a block towards 0)"""
+    if d <= 1:
+        return depth
+    x = depth.permute(2, 0, 1)[None]
+    valid = (x > 0).to(x.dtype)
+    s = F.avg_pool2d(x * valid, kernel_size=d, stride=d)
+    n = F.avg_pool2d(valid, kernel_size=d, stride=d)
+    return torch.where(n > 0, s / torch.clamp(n, min=1e-12), torch.zeros_like(s))[0].permute(1, 2, 0).contiguous()
+
+
+def depth_loss(depth: Tensor, gt_depth: Tensor, depth_lambda: float) -> Tensor:
+    """depth_lambda * mean over the pixels with gt_depth > 0 of |depth - gt_depth| (0 without a valid pixel); depth,
+    gt_depth [H,W,1] in scene units"""
+    valid = (gt_depth > 0).to(depth.dtype)
+    n = torch.clamp(valid.sum(), min=1.0)
+    return depth_lambda * (torch.abs(depth - gt_depth) * valid).sum() / n
+
+
 def scale_regularization(log_scales: Tensor, max_gauss_ratio: float = 10.0) -> Tensor:
     """Penalise needle-like Gaussians (PhysGaussian-style, as in splatfacto): mean(max(s_max/s_min, r) - r)."""
     s = torch.exp(log_scales)
@@ -122,20 +142,26 @@ TRAIN_AUTOGRAD = int(os.environ.get("GSD_TRAIN_AUTOGRAD", "0"))
 
 def one_call_route(model: SplatfactoDeblurModel) -> bool:
     """train_step renders through model.render_and_backward (step.render_step) unless the model lives on the CPU (host
-    logic tests with a stand-in render), the torch loss / autograd A/B switches are set, or training wants the depth
-    output (a forward-only extra the one-call route does not produce)"""
+    logic tests with a stand-in render), the torch loss / autograd A/B switches are set, or training wants get_outputs'
+    depth map every step (output_depth_during_training).  A depth LOSS runs on both routes (train_step gt_depth)"""
     return (model.means.is_cuda and not TORCH_TRAIN and not TRAIN_AUTOGRAD
             and not model.config.output_depth_during_training and "get_outputs" not in model.__dict__
             and type(model).get_outputs is SplatfactoDeblurModel.get_outputs)
 
 
 def train_step(model: SplatfactoDeblurModel, optimizers: Dict[str, torch.optim.Optimizer], camera: Camera,
-               gt_image: Tensor, ssim_lambda: float = 0.2, allreduce: Optional[str] = None) -> Dict[str, float]:
-    """One training iteration: render (HIP) -> loss -> backward (HIP) -> [DP gradient all-reduce] -> Adam."""
+               gt_image: Tensor, ssim_lambda: float = 0.2, allreduce: Optional[str] = None,
+               gt_depth: Optional[Tensor] = None, depth_lambda: float = 0.0) -> Dict[str, float]:
+    """One training iteration: render (HIP) -> loss -> backward (HIP) -> [DP gradient all-reduce] -> Adam.
+    gt_depth [H,W,1] (scene units, 0 = no measurement) with depth_lambda > 0 adds depth_loss(out["depth"], gt_depth)
+    to the loss, on either route (the depth map follows the resolution schedule: downscale_depth)."""
     model.train()
     for o in optimizers.values():
         o.zero_grad(set_to_none=True)
     gt_image = downscale_image(gt_image, model.downscale_factor())     # num_downscales resolution schedule
+    use_depth = gt_depth is not None and depth_lambda > 0
+    if use_depth:
+        gt_depth = downscale_depth(gt_depth.to(gt_image.device, torch.float32), model.downscale_factor())
     if one_call_route(model):
         # forward + backward of the frame as ONE host call (model.render_and_backward -> step.render_step): the HIP loss
         # kernel's forward already produces d loss / d rgb, so it sits between the two halves as a plain callable
@@ -145,16 +171,26 @@ def train_step(model: SplatfactoDeblurModel, optimizers: Dict[str, torch.optim.O
         def grad_image(rgb):
             box["loss"], v, _ = fused.image_loss_with_grad(rgb, gt_image, ssim_lambda)
             return v
-        rgb = model.render_and_backward(camera, grad_image)
+        grad_depth = None
+        if use_depth:
+            def grad_depth(depth, _accumulation):
+                depth = depth.requires_grad_(True)
+                box["depth_loss"] = dl = depth_loss(depth, gt_depth, depth_lambda)
+                return torch.autograd.grad(dl, depth)[0]
+        rgb = model.render_and_backward(camera, grad_image, grad_depth)
         loss = box["loss"]
+        if use_depth:
+            loss = loss + box["depth_loss"].detach()
         if model.config.use_scale_regularization:
             reg = scale_regularization(model.scales)
             reg.backward()
             loss = loss + reg.detach()
     else:
-        out = model.get_outputs(camera)
+        out = model.get_outputs(camera, return_depth=True) if use_depth else model.get_outputs(camera)
         rgb = out["rgb"].detach()
         loss = image_loss(out["rgb"], gt_image, ssim_lambda)
+        if use_depth:
+            loss = loss + depth_loss(out["depth"], gt_depth, depth_lambda)
         if model.config.use_scale_regularization:
             loss = loss + scale_regularization(model.scales)
         loss.backward()
@@ -214,10 +250,11 @@ def evaluate(model: SplatfactoDeblurModel, cameras, images, indices) -> Dict[str
 
 def train_scene(model: SplatfactoDeblurModel, scene, images, iterations: int, lr_scale: float = 1.0,
                 ssim_lambda: float = 0.2, optimize_eval_cameras: bool = False, eval_camera_every: int = 4,
-                densify=None, log_every: int = 0, seed: int = 0) -> Dict:
+                densify=None, log_every: int = 0, seed: int = 0, depths=None, depth_lambda: float = 0.0) -> Dict:
     """Train on scene.train_indices (one view per step, seeded shuffle), optionally refining the evaluation cameras
     in between; returns {'results': {psnr, ssim}, 'wall_clock_time_seconds', 'history'} like the reference's
-    metrics.json (/root/reference/train.py:87-100, parse_outputs.py:58)."""
+    metrics.json (/root/reference/train.py:87-100, parse_outputs.py:58).  depths (optional): per-frame depth maps
+    [H,W,1] or None, indexed like images (data.load_depth); with depth_lambda > 0 every step adds the depth loss."""
     import time
     optimizers = make_optimizers(model, lr_scale)
     g = torch.Generator().manual_seed(seed)
@@ -239,7 +276,8 @@ def train_scene(model: SplatfactoDeblurModel, scene, images, iterations: int, lr
         if not order:
             order = [scene.train_indices[j] for j in torch.randperm(len(scene.train_indices), generator=g).tolist()]
         i = order.pop()
-        h = train_step(model, optimizers, scene.cameras[i], images[i], ssim_lambda)
+        gd = depths[i] if depths is not None else None
+        h = train_step(model, optimizers, scene.cameras[i], images[i], ssim_lambda, gt_depth=gd, depth_lambda=depth_lambda)
         if densify is not None:
             from . import densify as D
             D.step_callback(model, optimizers, state, it, densify)

@@ -28,7 +28,8 @@
  *   [14] qx = -log2(e)/2 * conic.x        [15] qz = -log2(e)/2 * conic.z
  *   ([12..15]: per-entry constants of the compositors' validity test |u| <= nmid and of alpha = kmul * 2^u,
  *    u = the exponent of alpha shifted by nmid; written by the projection / gs_pack_records; opacity < 1/255: nmid = -1)
- * Gradient records / tuples: 12 floats, slots 0..8 of the same layout (9, 10: d loss / d pixel velocity).
+ * Gradient records / tuples: 12 floats, slots 0..8 of the same layout (9, 10: d loss / d pixel velocity; 11: d loss /
+ * d depth when a depth gradient is present, gs_frame_backward_depth).
  */
 #ifndef GSDEBLUR_H
 #define GSDEBLUR_H
@@ -134,7 +135,10 @@ int gs_project_fused_bwd(int N, int P, const float* means3d, const float* scales
                                           Gaussians with a scale ratio above 8 (needles) get by default; + 16
                                           (pixel-velocity model): v_records[.., 9..10] hold d loss / d pixel velocity
                                           from gs_rasterize_bwd_rs_slice; + 32 (needs touched): the kernel zero-fills the
-                                          gradient outputs and v_xy_sum itself — hand over uninitialised buffers*/,
+                                          gradient outputs and v_xy_sum itself — hand over uninitialised buffers; + 64:
+                                          v_records[.., 11] holds d loss / d camera-space depth (record float 9, from
+                                          gs_frame_backward_depth) and is chained to the means and the view matrices
+                                          (gs_project_pixvel_bwd: the mid-exposure view matrix only, no twist term)*/,
                          const float* sh_rest, int param_flags /*both as in gs_project_fused_fwd: the gradients returned
                                           are those of what was handed in (d/d log-scale, d/d logit)*/,
                          float* v_sh_rest /*[N*(K_stride-1)*3] iff sh_rest != NULL (v_sh is then [N*3])*/,
@@ -627,6 +631,16 @@ int gs_frame_backward(const gs_frame_state* state, const float* records, const f
                       float cmb_gamma, float cmb_min_level, int bwd_variant, float* v_records, unsigned char* touched,
                       const float* pix_vel /*as in the forward*/, const float* sample_times /*as in the forward*/,
                       void* arena, long long arena_bytes, void* stream);
+/* gs_frame_backward with a depth gradient: v_depth [S*H*W] or NULL = d loss / d out_depth of the forward (per sample image
+ * the sum over the blended splats of weight * camera-space depth; depth is a fourth colour channel with background 0).
+ * Non-NULL: v_records[.., 11] receives d loss / d record depth (float 9) besides the colour gradients — hand it to the
+ * projection backward with grad flag 64.  NULL: exactly gs_frame_backward (which calls this with NULL).  With v_depth,
+ * bwd_variant bit 1024 (the splat-parallel measurement form, no depth channel) is not honoured: the depth kernel runs. */
+int gs_frame_backward_depth(const gs_frame_state* state, const float* records, const float* background,
+                            const int* band_edges, const float* out_T, const float* v_img, const float* v_alpha,
+                            const float* cmb_scale, float cmb_gamma, float cmb_min_level, int bwd_variant,
+                            float* v_records, unsigned char* touched, const float* pix_vel, const float* sample_times,
+                            void* arena, long long arena_bytes, const float* v_depth /*[S*H*W] or NULL*/, void* stream);
 /* measurement only (not thread-safe): HIP events around the stages of the two calls above.  stage_mask bit i enables
  * stage i of {depth_sort, count_scan, slice_plan, slice_count, emit, tile_sort, bin_edges, raster_fwd, slice_sat,
  * raster_bwd, grad_reduce}; gs_frame_profile_read drains the pairs recorded since the last call (synchronising on
