@@ -16,6 +16,7 @@ from .ops import (  # noqa: F401
     bin_and_sort_records,
     render_subposes,
     render_combined,
+    render_batch,
     subpose_viewmats,
     subpose_schedule,
     combine_samples,

@@ -73,6 +73,9 @@ _SIGS = {
     "gs_combine_fwd": [_I, _L, _P, _F, _F, _P, _P],
     "gs_combine_bwd": [_I, _L, _P, _F, _F, _P, _P, _P, _P],
     "gs_combine_bwd_scale": [_I, _L, _F, _P, _P, _P, _P],
+    "gs_combine_fwd_batched": [_I, _I, _L, _P, _F, _F, _P, _P],
+    "gs_combine_bwd_batched": [_I, _I, _L, _P, _F, _F, _P, _P, _P, _P],
+    "gs_combine_bwd_scale_batched": [_I, _I, _L, _F, _P, _P, _P, _P],
     # host arrays (pointer table, widths) are passed as ctypes arrays -> plain pointers
     "gs_dp_row_mask": [_I, _I, _P, _P, _P, _P],
     "gs_dp_pack_rows": [_L, _P, _I, _P, _P, _P, _P],

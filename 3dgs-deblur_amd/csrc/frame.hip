@@ -34,7 +34,7 @@ extern "C" int gs_rasterize_bwd_slice_depth(const float* records, const int* sor
                                             const int* gi_of_e, float* tuples, unsigned char* flags,
                                             const int* sorted_ids, int n_records, const unsigned char* tile_hot,
                                             int variant, const float* cmb_scale, float cmb_gamma, float cmb_min_level,
-                                            const float* v_depth, void* stream);
+                                            const float* v_depth, int cameras, void* stream);
 extern "C" int gs_rasterize_bwd_rs_slice_depth(const float* records, const int* sorted_vals, const int* tile_bins,
                                                const int* band_edges, const float* background, int S, int H, int W,
                                                const float* out_T, const int* final_idx, const float* v_img,
@@ -289,6 +289,10 @@ GS_EXPORT int gs_frame_forward(const gs_frame_desc* dp, float* records, unsigned
   if (shared ? (d.P != 1 || d.R != 1 || !pix_vel || !sample_times) : (d.P != d.S * d.R)) return GS_ERR_INVALID;
   if (d.R > 1 && !band_tile_done) return GS_ERR_INVALID;
   if ((long long)d.S * d.H * d.W >= (1ll << 30)) return GS_ERR_INVALID;   // 32-bit byte offsets into [S,H,W] (raster.hip)
+  // several cameras in one frame: camera b owns sample images [b*S/B, (b+1)*S/B) and sub-poses [b*P/B, (b+1)*P/B); SE(3)
+  // sub-poses only (the pixel-velocity model and the shared list are single-camera forms)
+  const int cams = d.cameras > 1 ? d.cameras : 1;
+  if (cams > 1 && (d.S % cams != 0 || shared || pix_vel)) return GS_ERR_INVALID;
   // exact per-row rolling shutter (pixel-velocity model, raster_rs.hip) and shared-list frames: the records' tile boxes
   // are swept boxes, so the lists are built from the boxes themselves (no ellipse test, no hit masks) and the rs
   // compositors run
@@ -306,6 +310,7 @@ GS_EXPORT int gs_frame_forward(const gs_frame_desc* dp, float* records, unsigned
   if (host_pinned_bytes < 4 * (plan_ints + 1) + 64) return GS_ERR_INVALID;
   memset(state, 0, sizeof(*state));
   state->P = P; state->N = N; state->S = S; state->R = R; state->H = H; state->W = W;
+  state->cameras = cams;
   state->rolling_shutter_time = rs ? d.rolling_shutter_time : 0.f;
   state->shared_list = shared ? 1 : 0;
   Arena A(arena_ptr, arena_bytes);
@@ -703,6 +708,9 @@ GS_EXPORT int gs_frame_forward(const gs_frame_desc* dp, float* records, unsigned
     // has its average overwritten by the next
     auto average = [&]() -> int {
       if (!out_combined) return GS_OK;
+      if (cams > 1)
+        return gs_combine_fwd_batched(cams, S / cams, 3ll * H * W, out_img, d.combine_gamma, d.combine_min_level,
+                                      out_combined, st);
       return gs_combine_fwd(S, 3ll * H * W, out_img, d.combine_gamma, d.combine_min_level, out_combined, st);
     };
     if (last) CHECK(average());
@@ -800,7 +808,7 @@ GS_EXPORT int gs_frame_backward_depth(const gs_frame_state* state, const float* 
                                    reinterpret_cast<const int*>(base + sl.gi_of_e), tuples, flags,
                                    reinterpret_cast<const int*>(base + sl.sorted_ids), (int)std::min(n_rec, 2147483647ll),
                                    reinterpret_cast<const unsigned char*>(base + sl.tile_hot), bwd_variant, cmb_scale,
-                                   cmb_gamma, cmb_min_level, v_depth, st));
+                                   cmb_gamma, cmb_min_level, v_depth, state->cameras, st));
     }
     {
       StageScope sc(ST_REDUCE, st);

@@ -1285,6 +1285,7 @@ GS_EXPORT int gs_slice_colors(int n_slice, const unsigned* slice_gi, const unsig
   return gs_launch_status();
 }
 
+constexpr int GS_FLAG_XY_PER_CAMERA = 128;  // gs_project_fused_bwd: v_xy_sum is [B,N,2], B = bits 8..16 (see there)
 constexpr int GS_FLAG_ZERO_FILL = 32;     // sparse backward: zero-fill the dense gradient outputs in the kernel itself
 
 // bytes of scratch the ordered pose-gradient reduction of a projection backward takes (reduce_vV / pose_reduce_kernel):
@@ -1356,6 +1357,28 @@ static int launch_fused_bwd(const FusedParams& fp, int sh_degree, const float* r
   return gs_launch_status();
 }
 
+// Per-camera screen-space centre gradients (grad flag GS_FLAG_XY_PER_CAMERA): camera b owns sub-poses [b*Pc, (b+1)*Pc);
+// v_xy[b][i] = the sum over ITS sub-poses, in sub-pose order, of the xy gradient of every pair the compositor touched —
+// the sum fused_bwd_body forms for a single camera (vxs / vys), in the same order, so camera b's row equals that of
+// camera b rendered alone given the same v_records.  One thread per Gaussian, all B rows written (zeros included).
+__global__ __launch_bounds__(256) void xy_grad_cams_kernel(int N, int P, int B, const float* __restrict__ v_records,
+                                                           const unsigned char* __restrict__ touched,
+                                                           float* __restrict__ v_xy) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N) return;
+  const int Pc = P / B;
+  for (int b = 0; b < B; ++b) {
+    float vxs = 0.f, vys = 0.f;
+    for (int p = b * Pc; p < (b + 1) * Pc; ++p) {
+      const size_t idx = (size_t)p * N + i;
+      if (!touched[idx]) continue;
+      const float2 g = *reinterpret_cast<const float2*>(v_records + idx * kGradFloats);
+      vxs += g.x; vys += g.y;
+    }
+    *reinterpret_cast<float2*>(v_xy + ((size_t)b * N + i) * 2) = make_float2(vxs, vys);
+  }
+}
+
 // Scratch of the deterministic pose-gradient reduction (gs_project_bwd: P = 1, with_touched = 0; gs_project_fused_bwd /
 // gs_project_pixvel_bwd: with_touched = whether touched flags are passed).  Needed only when a view-matrix / twist
 // gradient is asked for.
@@ -1382,10 +1405,21 @@ GS_EXPORT int gs_project_fused_bwd(int N, int P, const float* means, const float
     return GS_ERR_INVALID;
   FusedParams fp = make_fused(N, P, means, scales, glob_scale, quats, opacities, sh, K_stride, sh_degree, viewmats,
                               fx, fy, cx, cy, H, W, clip, antialiased);
-  fp.flags = grad_flags; fp.act = param_flags; fp.sh_rest = sh_rest;
-  const FusedOut out = {v_means, v_scales, v_quats, v_opacities, v_sh, v_sh_rest, v_viewmats, v_xy_sum, nullptr, nullptr};
-  return launch_fused_bwd(fp, sh_degree, records, v_records, out, touched, pose_scratch, pose_scratch_bytes_,
-                          (hipStream_t)stream);
+  // per-camera xy gradients: the projection kernels run as for one camera without v_xy_sum (and see none of the
+  // flag's bits); one more launch sums each camera's sub-poses into its row of v_xy_sum [B,N,2]
+  const bool per_cam = (grad_flags & GS_FLAG_XY_PER_CAMERA) != 0;
+  const int cams = (grad_flags >> 8) & 0x1ff;
+  if (per_cam && (!touched || !v_xy_sum || cams < 1 || P % cams != 0)) return GS_ERR_INVALID;
+  fp.flags = per_cam ? (grad_flags & ~(GS_FLAG_XY_PER_CAMERA | (0x1ff << 8))) : grad_flags;
+  fp.act = param_flags; fp.sh_rest = sh_rest;
+  const FusedOut out = {v_means, v_scales, v_quats, v_opacities, v_sh, v_sh_rest, v_viewmats,
+                        per_cam ? nullptr : v_xy_sum, nullptr, nullptr};
+  const int rc = launch_fused_bwd(fp, sh_degree, records, v_records, out, touched, pose_scratch, pose_scratch_bytes_,
+                                  (hipStream_t)stream);
+  if (rc != GS_OK || !per_cam) return rc;
+  hipLaunchKernelGGL(xy_grad_cams_kernel, dim3((N + 255) / 256), dim3(256), 0, (hipStream_t)stream, N, P, cams, v_records,
+                     touched, v_xy_sum);
+  return gs_launch_status();
 }
 
 // ---- pixel-velocity model (the paper's first-order blur / rolling-shutter model; SURVEY App. A, C1;

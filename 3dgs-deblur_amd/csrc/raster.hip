@@ -557,6 +557,92 @@ __global__ __launch_bounds__(256) void combine_scale_kernel(int S, size_t n, flo
   }
 }
 
+// Grouped forms for a frame of B cameras (gs_frame_desc.cameras): sample images [B*S, n], averages [B, n].  Thread t
+// owns four consecutive elements of ONE camera (b = t / n4, j = 4 * (t % n4)) and runs, element for element, the
+// arithmetic of the single-camera kernel above, so camera b's result is bit-identical to that kernel on camera b's
+// S samples.  vec: n % 4 == 0 and every pointer 16-byte aligned (each camera's rows then are too).
+__global__ __launch_bounds__(256) void combine_fwd_batched_kernel(int B, int S, size_t n, const float* __restrict__ samples,
+                                                                  float gamma, float m, float* __restrict__ out, bool vec) {
+  const size_t n4 = (n + 3) / 4;
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (size_t)B * n4) return;
+  const size_t b = t / n4, i = (t - b * n4) * 4;
+  const float* cs = samples + b * (size_t)S * n;
+  float* co = out + b * n;
+  const float invS = 1.f / (float)S, ig = 1.f / gamma;
+  if (vec && i + 3 < n) {
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int k = 0; k < S; ++k) {
+      float4 c = *reinterpret_cast<const float4*>(cs + (size_t)k * n + i);
+      acc.x += combine_lin(c.x, gamma, m); acc.y += combine_lin(c.y, gamma, m);
+      acc.z += combine_lin(c.z, gamma, m); acc.w += combine_lin(c.w, gamma, m);
+    }
+    acc.x *= invS; acc.y *= invS; acc.z *= invS; acc.w *= invS;
+    if (gamma != 1.f) { acc.x = fast_pow(acc.x, ig); acc.y = fast_pow(acc.y, ig); acc.z = fast_pow(acc.z, ig); acc.w = fast_pow(acc.w, ig); }
+    *reinterpret_cast<float4*>(co + i) = acc;
+  } else {
+    for (size_t j = i; j < min(n, i + 4); ++j) {
+      float acc = 0.f;
+      for (int k = 0; k < S; ++k) acc += combine_lin(cs[(size_t)k * n + j], gamma, m);
+      acc *= invS;
+      co[j] = gamma != 1.f ? fast_pow(acc, ig) : acc;
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void combine_bwd_batched_kernel(int B, int S, size_t n, const float* __restrict__ samples,
+                                                                  float gamma, float m, const float* __restrict__ out,
+                                                                  const float* __restrict__ v_out,
+                                                                  float* __restrict__ v_samples, bool vec) {
+  const size_t n4 = (n + 3) / 4;
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (size_t)B * n4) return;
+  const size_t b = t / n4, i = (t - b * n4) * 4;
+  const float* cs = samples + b * (size_t)S * n;
+  float* cv = v_samples + b * (size_t)S * n;
+  const float* co = out + b * n;
+  const float* cvo = v_out + b * n;
+  const float invS = 1.f / (float)S;
+  if (vec && i + 3 < n) {
+    float4 o = *reinterpret_cast<const float4*>(co + i);
+    float4 vo = *reinterpret_cast<const float4*>(cvo + i);
+    float4 d = make_float4(combine_scale(o.x, vo.x, invS, gamma), combine_scale(o.y, vo.y, invS, gamma),
+                           combine_scale(o.z, vo.z, invS, gamma), combine_scale(o.w, vo.w, invS, gamma));
+    for (int k = 0; k < S; ++k) {
+      float4 c = *reinterpret_cast<const float4*>(cs + (size_t)k * n + i);
+      float4 g = make_float4(combine_grad(c.x, d.x, gamma, m), combine_grad(c.y, d.y, gamma, m),
+                             combine_grad(c.z, d.z, gamma, m), combine_grad(c.w, d.w, gamma, m));
+      *reinterpret_cast<float4*>(cv + (size_t)k * n + i) = g;
+    }
+  } else {
+    for (size_t j = i; j < min(n, i + 4); ++j) {
+      float dm = combine_scale(co[j], cvo[j], invS, gamma);
+      for (int k = 0; k < S; ++k) cv[(size_t)k * n + j] = combine_grad(cs[(size_t)k * n + j], dm, gamma, m);
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void combine_scale_batched_kernel(int B, int S, size_t n, float gamma,
+                                                                    const float* __restrict__ out,
+                                                                    const float* __restrict__ v_out,
+                                                                    float* __restrict__ scale, bool vec) {
+  const size_t n4 = (n + 3) / 4;
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (size_t)B * n4) return;
+  const size_t b = t / n4, i = (t - b * n4) * 4;
+  const float* co = out + b * n;
+  const float* cvo = v_out + b * n;
+  float* cs = scale + b * n;
+  const float invS = 1.f / (float)S;
+  if (vec && i + 3 < n) {
+    const float4 o = *reinterpret_cast<const float4*>(co + i), v = *reinterpret_cast<const float4*>(cvo + i);
+    *reinterpret_cast<float4*>(cs + i) = make_float4(combine_scale(o.x, v.x, invS, gamma), combine_scale(o.y, v.y, invS, gamma),
+                                                     combine_scale(o.z, v.z, invS, gamma), combine_scale(o.w, v.w, invS, gamma));
+  } else {
+    for (size_t j = i; j < min(n, i + 4); ++j) cs[j] = combine_scale(co[j], cvo[j], invS, gamma);
+  }
+}
+
 }  // namespace gs
 
 using namespace gs;
@@ -692,5 +778,40 @@ GS_EXPORT int gs_combine_bwd_scale(int S, long long n, float gamma, const float*
   unsigned blocks = (unsigned)((n + 1023) / 1024);
   hipLaunchKernelGGL(combine_scale_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, S, (size_t)n, gamma, out,
                      v_out, scale, vec);
+  return gs_launch_status();
+}
+
+// Grouped forms of the three calls above for B cameras in ONE launch: samples [B*S, n] (camera b's S sample images
+// contiguous), out / v_out / scale [B, n].  Camera b's rows are bit-identical to the single-camera call on its slice.
+static inline bool combine_vec(long long n, const void* a, const void* b, const void* c, const void* d) {
+  return (n % 4) == 0 && ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c) |
+                           reinterpret_cast<uintptr_t>(d)) & 15u) == 0;
+}
+static inline unsigned combine_batched_blocks(int B, long long n) {
+  return (unsigned)(((long long)B * ((n + 3) / 4) + 255) / 256);
+}
+
+GS_EXPORT int gs_combine_fwd_batched(int B, int S, long long n, const float* samples, float gamma, float min_level,
+                                     float* out, void* stream) {
+  if (B <= 0 || S <= 0 || n <= 0 || !samples || !out) return GS_ERR_INVALID;
+  hipLaunchKernelGGL(combine_fwd_batched_kernel, dim3(combine_batched_blocks(B, n)), dim3(256), 0, (hipStream_t)stream, B,
+                     S, (size_t)n, samples, gamma, min_level, out, combine_vec(n, samples, out, out, out));
+  return gs_launch_status();
+}
+
+GS_EXPORT int gs_combine_bwd_batched(int B, int S, long long n, const float* samples, float gamma, float min_level,
+                                     const float* out, const float* v_out, float* v_samples, void* stream) {
+  if (B <= 0 || S <= 0 || n <= 0 || !samples || !out || !v_out || !v_samples) return GS_ERR_INVALID;
+  hipLaunchKernelGGL(combine_bwd_batched_kernel, dim3(combine_batched_blocks(B, n)), dim3(256), 0, (hipStream_t)stream, B,
+                     S, (size_t)n, samples, gamma, min_level, out, v_out, v_samples,
+                     combine_vec(n, samples, out, v_out, v_samples));
+  return gs_launch_status();
+}
+
+GS_EXPORT int gs_combine_bwd_scale_batched(int B, int S, long long n, float gamma, const float* out, const float* v_out,
+                                           float* scale, void* stream) {
+  if (B <= 0 || S <= 0 || n <= 0 || !out || !v_out || !scale) return GS_ERR_INVALID;
+  hipLaunchKernelGGL(combine_scale_batched_kernel, dim3(combine_batched_blocks(B, n)), dim3(256), 0, (hipStream_t)stream,
+                     B, S, (size_t)n, gamma, out, v_out, scale, combine_vec(n, out, v_out, scale, scale));
   return gs_launch_status();
 }

@@ -487,7 +487,7 @@ __device__ __forceinline__ void pix_get(const BwdQuad& st, int k, float& T, floa
 // their names, which profiles/traffic.json's ISA hashes and tests/test_occupancy.py key on) exactly as they were.
 #define GS_BWD_NO_DEPTH_PARAM
 #define GS_BWD_DEPTH_PARAM , const float* __restrict__ v_depth
-#define GS_BWD_SLOAD_KERNEL(NAME, DEPTH, DEPTH_PARAM, PROLOGUE)                                                           \
+#define GS_BWD_SLOAD_KERNEL(NAME, DEPTH, DEPTH_PARAM, PROLOGUE, CMB_ROW)                                                        \
 template <bool STATE, int OUT>                                                                                          \
 __global__ __launch_bounds__(256, GS_BWD_SLOAD_WAVES) void NAME(                                                        \
     RasterParams prm, const int* __restrict__ ids /*record index per sorted entry, padded*/,                            \
@@ -534,7 +534,7 @@ _Pragma("unroll")                                                               
       if (DEPTH) vd = v_depth[pix];                                                                                                           \
       vr = v_img[pix * 3 + 0]; vg = v_img[pix * 3 + 1]; vb = v_img[pix * 3 + 2];                                                              \
       if (prm.cmb_scale) {                                                                                                                    \
-        const size_t q = ((size_t)y * prm.W + x) * 3;                                                                                         \
+        const size_t q = ((CMB_ROW) * prm.W + x) * 3;                                                                                        \
         vr = combine_grad(vr, prm.cmb_scale[q + 0], prm.cmb_gamma, prm.cmb_min);                                                              \
         vg = combine_grad(vg, prm.cmb_scale[q + 1], prm.cmb_gamma, prm.cmb_min);                                                              \
         vb = combine_grad(vb, prm.cmb_scale[q + 2], prm.cmb_gamma, prm.cmb_min);                                                              \
@@ -577,8 +577,17 @@ _Pragma("unroll")                                                               
   }                                                                                                                                           \
 }
 
-GS_BWD_SLOAD_KERNEL(raster_bwd_sload_kernel, false, GS_BWD_NO_DEPTH_PARAM, const float* const v_depth = nullptr; (void)v_depth;)
-GS_BWD_SLOAD_KERNEL(raster_bwd_depth_kernel, true, GS_BWD_DEPTH_PARAM, )
+GS_BWD_SLOAD_KERNEL(raster_bwd_sload_kernel, false, GS_BWD_NO_DEPTH_PARAM, const float* const v_depth = nullptr; (void)v_depth;,
+                    (size_t)y)
+GS_BWD_SLOAD_KERNEL(raster_bwd_depth_kernel, true, GS_BWD_DEPTH_PARAM, , (size_t)y)
+// frames of several cameras (gs_frame_desc.cameras > 1): sample image s belongs to camera s / s_cam, whose combine scale
+// is row block s / s_cam of cmb_scale [B,H,W,3].  Separately named instantiations (launched only for B > 1), so the two
+// default kernels above keep their names and instruction streams.
+#define GS_BWD_CAMS_PARAM , int s_cam
+#define GS_BWD_DEPTH_CAMS_PARAM , const float* __restrict__ v_depth, int s_cam
+GS_BWD_SLOAD_KERNEL(raster_bwd_sload_cams_kernel, false, GS_BWD_CAMS_PARAM,
+                    const float* const v_depth = nullptr; (void)v_depth;, (size_t)(s / s_cam) * prm.H + y)
+GS_BWD_SLOAD_KERNEL(raster_bwd_depth_cams_kernel, true, GS_BWD_DEPTH_CAMS_PARAM, , (size_t)(s / s_cam) * prm.H + y)
 
 // ---------------------------------------------------------------------------
 // Splat-parallel backward (round 6; VERDICT round 5 item 2a: "build, not cost").  MEASURED NEGATIVE, kept selectable
@@ -926,6 +935,9 @@ GS_EXPORT int gs_rasterize_bwd(const float* records, const int* sorted_vals, con
 // gs_rasterize_bwd_slice_depth (library-internal: csrc/frame.hip) takes v_depth [S,H,W] = d loss / d depth_acc as well:
 // non-NULL selects the depth specialisations of the scalar-cache kernels, tuple form only (tuple slot 11 = d loss /
 // d depth); the round-1 and splat-parallel kernels have none (variant 1024 is not honoured with a depth gradient).
+// cameras > 1 (a frame of several cameras, S = cameras * samples per camera) with cmb_scale [cameras,H,W,3]: the
+// camera-indexed instantiations, tuple form and variant 0 only (anything else is refused).  Without cmb_scale (v_img
+// holds the per-sample gradients) the camera count changes nothing.
 extern "C" int gs_rasterize_bwd_slice_depth(const float* records, const int* sorted_vals, const int* tile_bins,
                                             const int* band_edges, const float* background, int S, int R, int H, int W,
                                             const float* out_T, const int* final_idx, const float* v_img,
@@ -933,7 +945,7 @@ extern "C" int gs_rasterize_bwd_slice_depth(const float* records, const int* sor
                                             const int* gi_of_e, float* tuples, unsigned char* flags,
                                             const int* sorted_ids, int n_records, const unsigned char* tile_hot,
                                             int variant, const float* cmb_scale, float cmb_gamma, float cmb_min_level,
-                                            const float* v_depth, void* stream) {
+                                            const float* v_depth, int cameras, void* stream) {
   if (S <= 0 || R <= 0 || H <= 0 || W <= 0) return GS_ERR_INVALID;
   RasterParams prm = make_raster_params(records, sorted_vals, tile_bins, band_edges, background, S, R, H, W);
   prm.gi_of_e = gi_of_e;
@@ -947,6 +959,32 @@ extern "C" int gs_rasterize_bwd_slice_depth(const float* records, const int* sor
   // scalar-cache kernels: record index per sorted entry = sorted_ids, or sorted_vals itself when it holds Gaussian ids
   const int* ids = sorted_ids ? sorted_ids : (gi_of_e ? nullptr : sorted_vals);
   const unsigned max_id = (unsigned)(n_records > 0 ? n_records - 1 : 0);
+  if (cameras > 1 && cmb_scale) {
+    // several cameras, fused combine: the camera-indexed instantiations (tuple form, the default variant only; the
+    // splat-parallel measurement form and the round-1 kernels read one camera's scale and refuse a batch)
+    if (S % cameras != 0) return GS_ERR_INVALID;
+    const int s_cam = S / cameras;
+    if ((variant & ~1024) || (!v_depth && variant != 0)) return GS_ERR_INVALID;
+    if (n_records <= 0 || !ids || !tup) return GS_ERR_INVALID;
+    const bool state = bwd_T && bwd_B;
+    if (v_depth && state)
+      hipLaunchKernelGGL((raster_bwd_depth_cams_kernel<true, 1>), dim3(blocks), dim3(256), 0, st, prm, ids, sorted_vals,
+                         records, max_id, out_T, final_idx, v_img, v_alpha, v_records, blocks, bwd_T, bwd_B, tuples,
+                         flags, tile_hot, v_depth, s_cam);
+    else if (v_depth)
+      hipLaunchKernelGGL((raster_bwd_depth_cams_kernel<false, 1>), dim3(blocks), dim3(256), 0, st, prm, ids, sorted_vals,
+                         records, max_id, out_T, final_idx, v_img, v_alpha, v_records, blocks, (float*)nullptr,
+                         (float*)nullptr, tuples, flags, tile_hot, v_depth, s_cam);
+    else if (state)
+      hipLaunchKernelGGL((raster_bwd_sload_cams_kernel<true, 1>), dim3(blocks), dim3(256), 0, st, prm, ids, sorted_vals,
+                         records, max_id, out_T, final_idx, v_img, v_alpha, v_records, blocks, bwd_T, bwd_B, tuples,
+                         flags, tile_hot, s_cam);
+    else
+      hipLaunchKernelGGL((raster_bwd_sload_cams_kernel<false, 1>), dim3(blocks), dim3(256), 0, st, prm, ids, sorted_vals,
+                         records, max_id, out_T, final_idx, v_img, v_alpha, v_records, blocks, (float*)nullptr,
+                         (float*)nullptr, tuples, flags, tile_hot, s_cam);
+    return gs_launch_status();
+  }
   if (v_depth) {
     // the depth kernels exist in the tuple form only (what gs_frame_backward_depth runs); variant bit 1024 (the
     // splat-parallel measurement form, which has no depth channel) is not honoured here: the depth kernel runs
@@ -1018,7 +1056,7 @@ GS_EXPORT int gs_rasterize_bwd_slice(const float* records, const int* sorted_val
   return gs_rasterize_bwd_slice_depth(records, sorted_vals, tile_bins, band_edges, background, S, R, H, W, out_T,
                                       final_idx, v_img, v_alpha, bwd_T, bwd_B, v_records, gi_of_e, tuples, flags,
                                       sorted_ids, n_records, tile_hot, variant, cmb_scale, cmb_gamma, cmb_min_level,
-                                      nullptr, stream);
+                                      nullptr, 1, stream);
 }
 
 // Sum each slice Gaussian's gradient tuples (written by gs_rasterize_bwd_slice with tuples != NULL) into

@@ -64,7 +64,20 @@ class DensifyState:
 
     @torch.no_grad()
     def after_backward(self, radii: Tensor, xy_grad: Tensor, width: int, height: int) -> None:
-        """radii int32 [P,N] (0 = culled in that sub-pose), xy_grad float32 [N,2] in pixels."""
+        """radii int32 [P,N] (0 = culled in that sub-pose), xy_grad float32 [N,2] in pixels.  A batch of B cameras
+        (render_batch): xy_grad [B,N,2] and radii [B,P,N] — each camera counts as one observation, exactly as B calls
+        with one camera each."""
+        if isinstance(xy_grad, (list, tuple)):
+            # cameras rendered in several frames (model.get_outputs_batch with mixed intrinsics): per-camera tensors
+            for r, g in zip(radii, xy_grad):
+                self.after_backward(r, g, width, height)
+            return
+        if xy_grad.dim() == 3:
+            if radii.dim() != 3 or radii.shape[0] != xy_grad.shape[0]:
+                raise ValueError("a batch's xy_grad [B,N,2] needs radii [B,P,N]")
+            for b in range(xy_grad.shape[0]):
+                self.after_backward(radii[b], xy_grad[b], width, height)
+            return
         radii = radii.reshape(-1, radii.shape[-1])
         visible = (radii > 0).any(dim=0)
         self.xys_grad_norm += torch.where(visible, xy_grad.norm(dim=-1), torch.zeros_like(self.xys_grad_norm))

@@ -435,6 +435,103 @@ class SplatfactoDeblurModel(nn.Module):
             return 1
         return 2 ** max(int(self.config.num_downscales) - int(self.step) // max(1, int(self.config.resolution_schedule)), 0)
 
+    def _batch_groups(self, cameras):
+        """(rescaled camera, S, R, times) per camera, grouped by what one frame must share — fx, fy, cx, cy, H, W, S,
+        R — in the order of each group's first camera: [(key, [input positions])]"""
+        d = self.downscale_factor()
+        items, groups = [], {}
+        for j, cam in enumerate(cameras):
+            if d > 1:
+                cam = cam.rescaled(d)          # each camera follows the resolution schedule, as in get_outputs
+            S, R, times = self._schedule(cam)
+            items.append((cam, S, R, times))
+            key = (float(cam.fx), float(cam.fy), float(cam.cx), float(cam.cy), int(cam.height), int(cam.width), S, R)
+            groups.setdefault(key, []).append(j)
+        return items, list(groups.items())
+
+    def _render_group(self, items, return_depth: bool, detach_gaussians: bool = False):
+        """ONE ops.render_batch frame for cameras that share intrinsics, size, S and R: each camera keeps its own pose
+        and velocity adjustments (by cam_idx), exposure and rolling-shutter schedule"""
+        cfg = self.config
+        dev = self.means.device
+        cam0, S, R, _ = items[0]
+        vms = []
+        for cam, _, _, times in items:
+            viewmat, lin, ang = self._viewmat_and_velocity(cam)
+            vms.append(ops.subpose_viewmats(viewmat, lin, ang, self._const(times)))
+        viewmats = torch.stack(vms)
+        gp = (self.means, self.scales, self.quats, self.opacities, self.features_dc, self.features_rest)
+        if detach_gaussians:
+            gp = tuple(t.detach() for t in gp)
+        means_, scales_, quats_, opac_, dc_, rest_ = gp
+        bg = self._background(dev)
+        use_gamma = cfg.blur_samples > 0
+        xy = None
+        if self.training and self.collect_densify_stats and not detach_gaussians:
+            xy = torch.zeros(len(items), self.num_points, 2, device=dev)
+        idx = [c.metadata.get("cam_idx") if c.metadata else None for c, _, _, _ in items]
+        hints = self.frame_hints if any(i is None for i in idx) else self.frame_hints.view(("batch",) + tuple(int(i) for i in idx))
+        res = ops.render_batch(
+            means_, scales_, quats_, opac_.reshape(-1), dc_, viewmats, bg, S, R, cam0.fx, cam0.fy, cam0.cx, cam0.cy,
+            cam0.height, cam0.width, gamma=cfg.gamma if use_gamma else 1.0,
+            min_rgb_level=cfg.min_rgb_level if use_gamma else 0.0, sh_degree=self.active_sh_degree(),
+            antialiased=(cfg.rasterize_mode == "antialiased"), return_depth=return_depth, sh_rest=rest_,
+            raw_params=True, xy_grad_out=xy, hints=hints)
+        return res, xy, bg
+
+    def get_outputs_batch(self, cameras, detach_gaussians: bool = False,
+                          return_depth: Optional[bool] = None) -> Dict:
+        """get_outputs for a list of cameras through ops.render_batch: one frame per group of cameras that share
+        intrinsics, size, blur samples and row bands (groups in the order of their first camera; outputs in input
+        order).  -> {"rgb" [B,H,W,3], "depth" [B,H,W,1] or None, "accumulation" [B,H,W,1], "background"}; when the
+        cameras' sizes differ, "rgb" / "depth" / "accumulation" are lists of per-camera tensors instead.
+        Training keeps self.radii [B,S*R,N] and self.xy_grad [B,N,2] per camera (lists of per-camera tensors for
+        several groups).  SE(3) motion model only."""
+        cfg = self.config
+        if cfg.motion_model != "se3":
+            raise NotImplementedError("get_outputs_batch renders the SE(3) motion model; the pixel-velocity model renders "
+                                      "one camera per call (get_outputs)")
+        cameras = list(cameras)
+        if not cameras:
+            raise ValueError("get_outputs_batch needs at least one camera")
+        want_depth = (cfg.output_depth_during_training or not self.training) if return_depth is None else bool(return_depth)
+        items, groups = self._batch_groups(cameras)
+        rgb, acc, depth, radii, xys = ([None] * len(cameras) for _ in range(5))
+        bg = None
+        for _, pos in groups:
+            (g_rgb, g_alphas, g_radii, *g_depth), g_xy, bg = self._render_group([items[j] for j in pos], want_depth,
+                                                                                detach_gaussians)
+            g_acc = g_alphas.mean(dim=1)[..., None]
+            g_dep = [expected_depth(g_depth[0][k], g_alphas[k]) for k in range(len(pos))] if want_depth else None
+            for k, j in enumerate(pos):
+                rgb[j], acc[j], radii[j] = torch.clamp(g_rgb[k], max=1.0), g_acc[k], g_radii[k]
+                depth[j] = g_dep[k] if g_dep is not None else None
+                xys[j] = g_xy[k] if g_xy is not None else None
+        same = len({tuple(r.shape) for r in rgb}) == 1
+        if len(groups) == 1:
+            # one frame: the batch's own tensors (its backward writes the xy_grad rows)
+            self.radii, self.xy_grad = g_radii, g_xy
+        else:
+            self.radii, self.xy_grad = radii, (None if xys[0] is None else xys)
+        self.last_size = (items[0][0].width, items[0][0].height)
+        out = {"background": bg}
+        if same:
+            out["rgb"], out["accumulation"] = torch.stack(rgb), torch.stack(acc)
+            out["depth"] = torch.stack(depth) if want_depth else None
+        else:
+            out["rgb"], out["accumulation"], out["depth"] = rgb, acc, (depth if want_depth else None)
+        return out
+
+    @torch.no_grad()
+    def get_outputs_for_cameras(self, cameras) -> Dict:
+        """no_grad eval form of get_outputs_batch (the batched get_outputs_for_camera)"""
+        was = self.training
+        self.eval()
+        try:
+            return self.get_outputs_batch(cameras)
+        finally:
+            self.train(was)
+
     @torch.no_grad()
     def get_outputs_for_camera(self, camera: Camera) -> Dict[str, Tensor]:
         """Eval entry point used by /root/reference/render_model.py:217."""

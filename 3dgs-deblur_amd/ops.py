@@ -585,7 +585,8 @@ class _FrameDesc(ctypes.Structure):
                                                                                      ("select_cap", ctypes.c_int),
                                                                                      ("sweep_t_min", ctypes.c_float),
                                                                                      ("sweep_t_max", ctypes.c_float),
-                                                                                     ("lazy_records", ctypes.c_void_p)]
+                                                                                     ("lazy_records", ctypes.c_void_p),
+                                                                                     ("cameras", ctypes.c_int)]
 
 
 class _ProjectInputs(ctypes.Structure):
@@ -606,7 +607,7 @@ class _FrameState(ctypes.Structure):
                 [("rolling_shutter_time", ctypes.c_float), ("shared_list", ctypes.c_int), ("depth_select", ctypes.c_int),
                  ("select_overflow", ctypes.c_int), ("open_after_first", ctypes.c_float)] +
                 [(k, ctypes.c_longlong) for k in ("n_total", "max_selected", "arena_used", "arena_required")] +
-                [("slice", _FrameSlice * 16)])
+                [("slice", _FrameSlice * 16), ("cameras", ctypes.c_int)])
 
 
 def _box_share(state) -> Optional[float]:
@@ -742,12 +743,13 @@ def native_frame_forward(records: Tensor, depth_keys: Tensor, num_tiles_hit: Ten
                          H: int, W: int, bg: Tensor, edges: Tensor, slice_base: int, color=None,
                          out_depth: Optional[Tensor] = None, reserve_backward: bool = True, rs=None, combine=None,
                          hints: Optional[FrameHints] = None, band_clipped: bool = False, lazy=None,
-                         depth_select: Optional[bool] = None):
+                         depth_select: Optional[bool] = None, cameras: int = 1):
     """combine = (gamma, min_level, out [H,W,3]): the library launches the gamma-space average of the sample images itself,
     behind every slice's compositor (it overlaps the open-tile read-back).  rs = (pix_vel [N,2], rolling_shutter_time[, sample_times [S]]) or None; with sample_times the frame runs in the
     shared-list mode (P == 1: one record set and one tile list for the S samples).  gs_frame_forward: -> (out_img [S,H,W,3], out_T [S,H,W], frame) ; frame = dict(arena, state) for
     native_frame_backward.  Raises _ArenaTooSmall (after recording a larger size) when the arena did not hold the frame:
-    the caller projects again (the depth keys were consumed) and calls once more."""
+    the caller projects again (the depth keys were consumed) and calls once more.  cameras = B > 1: the frame holds B
+    cameras of S / B sample images each (gs_frame_desc.cameras); combine's out is then [B,H,W,3]."""
     global last_num_intersects, _slice_totals, last_depth_select
     L = _L()
     dev = records.device
@@ -780,7 +782,7 @@ def native_frame_forward(records: Tensor, depth_keys: Tensor, num_tiles_hit: Ten
                       int(bool(band_clipped)), int(bool(depth_select and slice_base > 0)),
                       int(min(hints.select_cap, 2 ** 31 - 1)) if depth_select else 0,
                       float(rs[3][0]) if shared and len(rs) > 3 else 0.0, float(rs[3][1]) if shared and len(rs) > 3 else 0.0,
-                      ctypes.addressof(lazy) if lazy is not None else None)
+                      ctypes.addressof(lazy) if lazy is not None else None, int(cameras))
     state = _FrameState()
     out_img = torch.empty(S, H, W, 3, device=dev)
     out_T = torch.empty(S, H, W, device=dev)
@@ -1182,7 +1184,7 @@ class _RenderSubposes(Function):
     def forward(ctx, means3d, scales, quats, opacities, sh, viewmats, background, S, R, fx, fy, cx, cy,
                 img_height, img_width, sh_degree, antialiased, glob_scale, clip_thresh, xy_grad_out, return_alpha,
                 gamma, min_rgb_level, lin_vel=None, ang_vel=None, times=None, return_depth=False, rs_time=0.0,
-                sh_rest=None, param_flags=0, shared_list=False, hints=None):
+                sh_rest=None, param_flags=0, shared_list=False, hints=None, cameras=1):
         # an output the loss does not use arrives as None in backward instead of a materialised zero tensor
         ctx.set_materialize_grads(False)
         means3d, scales, quats = _f32(means3d, "means3d"), _f32(scales, "scales"), _f32(quats, "quats")
@@ -1194,10 +1196,15 @@ class _RenderSubposes(Function):
             sh_rest = _f32(sh_rest, "sh_rest")
             if sh.reshape(sh.shape[0], -1).shape[1] != 3 or sh_rest.dim() != 3 or sh_rest.shape[0] != sh.shape[0]:
                 raise ValueError("with sh_rest [N,K-1,3], sh must be features_dc [N,3] (or [N,1,3])")
+        # B > 1 cameras in one frame (render_batch): S and the viewmats span all of them, camera b owns sample images
+        # [b*S/B, (b+1)*S/B) and sub-poses [b*P/B, (b+1)*P/B)
+        B = max(1, int(cameras))
+        xy_shape = (means3d.shape[0], 2) if B == 1 else (B, means3d.shape[0], 2)
         if xy_grad_out is not None:
-            if (xy_grad_out.shape != (means3d.shape[0], 2) or xy_grad_out.dtype != torch.float32
+            if (xy_grad_out.shape != xy_shape or xy_grad_out.dtype != torch.float32
                     or not xy_grad_out.is_contiguous() or xy_grad_out.device != means3d.device):
-                raise ValueError("xy_grad_out must be a contiguous float32 [N,2] tensor on the Gaussians' device")
+                raise ValueError(f"xy_grad_out must be a contiguous float32 {list(xy_shape)} tensor on the Gaussians' "
+                                 f"device")
         ctx.xy_grad_out = xy_grad_out
         N, K = means3d.shape[0], (sh.shape[1] if sh_rest is None else 1 + sh_rest.shape[1])
         P = S * R
@@ -1255,10 +1262,14 @@ class _RenderSubposes(Function):
         # before the depth pre-sort instead of being keyed, sorted, scanned and planned for nothing)
         if backend is None and R > 1 and BAND_AWARE:
             defer_flags |= 4 | (R << 8)
+        if B > 1 and (pixvel or shared is not None or backend is not None):
+            raise NotImplementedError("a frame of several cameras renders SE(3) sub-poses through the library's frame "
+                                      "path (no pixel-velocity model, shared list or frame backend)")
         if backend is None and hints is None:
             # default owner of the frame-to-frame hints: the scene's shape AND its parameter storage, so that two
-            # scenes of one shape do not share a budget / arena estimate
-            hints = hints_for((str(dev), N, P, S, H, W, shared is not None, means3d.untyped_storage().data_ptr()))
+            # scenes of one shape do not share a budget / arena estimate (and the camera count of a batch)
+            key = (str(dev), N, P, S, H, W, shared is not None, means3d.untyped_storage().data_ptr())
+            hints = hints_for(key if B == 1 else key + (B,))
         # lazy records (see LAZY_RECORDS): SE(3) sub-poses through the library's frame path, planned slices, and a scene
         # whose frames have so far stopped within the default budget
         lazy = None
@@ -1321,14 +1332,15 @@ class _RenderSubposes(Function):
             # fused sub-frame averaging: the library launches it behind the last compositor (below: `averaged`)
             averaged = None
             if gamma is not None:
-                averaged = (float(gamma), float(min_rgb_level) / 255.0, torch.empty(H, W, 3, device=dev))
+                averaged = (float(gamma), float(min_rgb_level) / 255.0,
+                            torch.empty((H, W, 3) if B == 1 else (B, H, W, 3), device=dev))
             retries = 0
             for attempt in range(_ARENA_ATTEMPTS):
                 try:
                     out_img, out_T, ctx.frame = native_frame_forward(records, dkeys, ntiles, P, N, S, R, H, W, bg, edges,
                                                                      hints.slice_base(), color, depth_acc,
                                                                      any(ctx.needs_input_grad), rs, averaged, hints,
-                                                                     bool(defer_flags & 4), lazy)
+                                                                     bool(defer_flags & 4), lazy, cameras=B)
                     hints.feedback(int(ctx.frame["state"].n_slices), retries, _box_share(ctx.frame["state"]),
                                    int(ctx.frame["state"].depth_select), float(ctx.frame["state"].open_after_first),
                                    int(ctx.frame["state"].max_selected), int(ctx.frame["state"].select_overflow))
@@ -1376,7 +1388,8 @@ class _RenderSubposes(Function):
         ctx.n_isect = n_isect
         ctx.bg_grad = background is not None and ctx.needs_input_grad[6]
         ctx.mark_non_differentiable(radii)
-        ctx.img_shape = (S, H, W, 3) if gamma is None else (H, W, 3)
+        ctx.img_shape = (S, H, W, 3) if gamma is None else ((H, W, 3) if B == 1 else (B, H, W, 3))
+        ctx.cameras = B
         return first, (1.0 - out_T) if return_alpha else None, radii, depth_acc
 
     @staticmethod
@@ -1388,7 +1401,8 @@ class _RenderSubposes(Function):
         dev = means3d.device
         L = _L()
         if v_img is None and v_alpha is None and v_depth is None:
-            return (None,) * 32
+            return (None,) * 33
+        B = ctx.cameras
         if v_depth is not None:
             # d loss / d depth_acc [S,H,W]: the depth specialisations of the native frame backward (grad flag 64 below)
             if ctx.frame is None:
@@ -1404,14 +1418,22 @@ class _RenderSubposes(Function):
             if ctx.bg_grad:
                 # a learnable background needs the per-sample gradients themselves: two-step backward
                 v_samples = torch.empty_like(samples)
-                _check(L.gs_combine_bwd(S, rgb.numel(), _ptr(samples), gamma, m, _ptr(rgb), _ptr(v_img),
-                                        _ptr(v_samples), _stream()), "combine_bwd")
+                if B > 1:
+                    _check(L.gs_combine_bwd_batched(B, S // B, rgb.numel() // B, _ptr(samples), gamma, m, _ptr(rgb),
+                                                    _ptr(v_img), _ptr(v_samples), _stream()), "combine_bwd_batched")
+                else:
+                    _check(L.gs_combine_bwd(S, rgb.numel(), _ptr(samples), gamma, m, _ptr(rgb), _ptr(v_img),
+                                            _ptr(v_samples), _stream()), "combine_bwd")
                 v_img = v_samples
             else:
                 scale = torch.empty_like(rgb)
                 with _stage("combine"):
-                    _check(L.gs_combine_bwd_scale(S, rgb.numel(), gamma, _ptr(rgb), _ptr(v_img), _ptr(scale),
-                                                  _stream()), "combine_bwd_scale")
+                    if B > 1:
+                        _check(L.gs_combine_bwd_scale_batched(B, S // B, rgb.numel() // B, gamma, _ptr(rgb), _ptr(v_img),
+                                                              _ptr(scale), _stream()), "combine_bwd_scale_batched")
+                    else:
+                        _check(L.gs_combine_bwd_scale(S, rgb.numel(), gamma, _ptr(rgb), _ptr(v_img), _ptr(scale),
+                                                      _stream()), "combine_bwd_scale")
                 combine = (scale, gamma, m)
                 v_img = samples
         # atomic-free path: only Gaussians the compositor touched get a gradient record (plain stores) and a
@@ -1445,6 +1467,8 @@ class _RenderSubposes(Function):
         need_v = ctx.needs_input_grad[5]
         xy_out = ctx.xy_grad_out
         fill_flag = (32 if touched is not None else 0) | (64 if v_depth is not None else 0)     # 64: v_records[:, 11]
+        # 128 | B << 8: xy_grad_out is [B,N,2], one row per camera (a batch always has touched flags)
+        xy_cams = (128 | (B << 8)) if (B > 1 and xy_out is not None) else 0
         pf = ctx.param_flags
         v_lin = v_ang = None
         # scratch of the ordered camera-gradient reduction (the sparse form runs when touched flags exist)
@@ -1474,11 +1498,11 @@ class _RenderSubposes(Function):
                                               _ptr(sh), K, deg, _ptr(V), fx, fy, cx, cy, H, W, clip, aa, _ptr(records),
                                               _ptr(v_records), _ptr(v_means), _ptr(v_scales), _ptr(v_quats),
                                               _ptr(v_opac), _ptr(v_sh), _ptr(v_V), _ptr(touched), _ptr(xy_out),
-                                              _proj_grad_flags() | fill_flag, _ptr(sh_rest), pf, _ptr(v_sh_rest),
+                                              _proj_grad_flags() | fill_flag | xy_cams, _ptr(sh_rest), pf, _ptr(v_sh_rest),
                                               _ptr(psc), psc_n, _stream()), "project_fused_bwd")
         v_bg = (out_T[..., None] * v_img).sum(dim=(0, 1, 2)) if ctx.bg_grad else None
         return ((v_means, v_scales, v_quats, v_opac, v_sh, v_V, v_bg) + (None,) * 16
-                + (v_lin, v_ang, None, None, None, v_sh_rest, None, None, None))
+                + (v_lin, v_ang, None, None, None, v_sh_rest, None, None, None, None))
 
 
 def render_subposes(means3d: Tensor, scales: Tensor, quats: Tensor, opacities: Tensor, sh: Tensor,
@@ -1543,6 +1567,78 @@ def render_combined(means3d: Tensor, scales: Tensor, quats: Tensor, opacities: T
                                 bool(return_depth), float(rolling_shutter_time), sh_rest, 3 if raw_params else 0,
                                 bool(shared_list), hints)
     return out if return_depth else out[:3]
+
+
+# 32-bit pixel offsets of the compositors (gs_frame_forward): sample images x H x W of ONE frame, the whole batch
+MAX_FRAME_PIXELS = 1 << 30
+
+
+def check_batch(n_cameras: int, blur_samples: int, rs_bands: int, img_height: int, img_width: int) -> None:
+    """host-side limits of one frame of B cameras (render_batch): B*S*R sub-poses <= MAX_SUBPOSES and
+    B*S*H*W < MAX_FRAME_PIXELS; raises ValueError naming the limit before anything is launched"""
+    B, S, R = int(n_cameras), int(blur_samples), int(rs_bands)
+    if B < 1:
+        raise ValueError("render_batch needs at least one camera")
+    if B * S * R > MAX_SUBPOSES:
+        raise ValueError(f"{B} cameras x {S} blur samples x {R} row bands = {B * S * R} sub-poses in one frame; a frame "
+                         f"holds at most {MAX_SUBPOSES} (kMaxSubposes): render fewer cameras per call")
+    if B * S * int(img_height) * int(img_width) >= MAX_FRAME_PIXELS:
+        raise ValueError(f"{B} cameras x {S} blur samples x {img_height}x{img_width} pixels = "
+                         f"{B * S * int(img_height) * int(img_width)} sample pixels in one frame; the compositors' 32-bit "
+                         f"offsets need fewer than 2^30: render fewer cameras per call")
+
+
+def render_batch(means3d: Tensor, scales: Tensor, quats: Tensor, opacities: Tensor, sh: Tensor, viewmats: Tensor,
+                 background: Optional[Tensor], blur_samples: int, rs_bands: int, fx: float, fy: float, cx: float,
+                 cy: float, img_height: int, img_width: int, gamma: float = 1.0, min_rgb_level: float = 0.0,
+                 sh_degree: int = 3, antialiased: bool = True, glob_scale: float = 1.0, clip_thresh: float = 0.01,
+                 return_alpha: bool = True, return_depth: bool = False, sh_rest: Optional[Tensor] = None,
+                 raw_params: bool = False, xy_grad_out: Optional[Tensor] = None, hints: Optional[FrameHints] = None,
+                 times: Optional[Tensor] = None, shared_list: bool = False):
+    """B cameras in ONE frame and ONE autograd node: render_combined for each camera, with the per-frame costs (launches,
+    read-backs) paid once.  viewmats [B, S*R, 4, 4]: camera b's S*R SE(3) sub-pose viewmats in render_combined's order
+    (gradients reach them, hence each camera's viewmat and velocities through subpose_viewmats).  The cameras share
+    fx, fy, cx, cy, H, W, S, R, gamma and min_rgb_level.
+    -> (rgb [B,H,W,3], alphas [B,S,H,W] or None, radii int32 [B,S*R,N]) and depth_acc [B,S,H,W] with return_depth.
+    xy_grad_out (optional float32 [B,N,2]) is OVERWRITTEN during backward: row b is camera b's sum over its sub-poses
+    of the screen-space centre gradient (render_combined's statistic, per camera).
+    Limits: B*S*R <= MAX_SUBPOSES and B*S*H*W < 2^30 (check_batch).  The pixel-velocity model (times) and the shared
+    list are single-camera forms (NotImplementedError), as is the Python frame backend.  B == 1 is render_combined."""
+    if times is not None:
+        raise NotImplementedError("render_batch renders SE(3) sub-poses; the pixel-velocity model (times=) renders one "
+                                  "camera per call (render_combined)")
+    if shared_list:
+        raise NotImplementedError("render_batch has no shared-list mode (pixel-velocity model, one camera per call)")
+    if frame_backend is not None and not frame_backend.native_ok():
+        raise NotImplementedError("render_batch runs through the library's frame path only; the Python frame backend "
+                                  "renders one camera per call")
+    S, R = max(1, int(blur_samples)), max(1, int(rs_bands))
+    if viewmats.dim() != 4 or tuple(viewmats.shape[1:]) != (S * R, 4, 4):
+        raise ValueError(f"viewmats must be [B,{S * R},4,4] (B cameras x {S} blur samples x {R} row bands)")
+    B = int(viewmats.shape[0])
+    H, W = int(img_height), int(img_width)
+    check_batch(B, S, R, H, W)
+    N = means3d.shape[0]
+    if xy_grad_out is not None and tuple(xy_grad_out.shape) != (B, N, 2):
+        raise ValueError(f"xy_grad_out must be [B,N,2] = [{B},{N},2]")
+    if B == 1:
+        out = _RenderSubposes.apply(means3d, scales, quats, opacities, sh, viewmats[0], background, S, R, fx, fy, cx, cy,
+                                    H, W, sh_degree, antialiased, glob_scale, clip_thresh,
+                                    None if xy_grad_out is None else xy_grad_out[0], bool(return_alpha), float(gamma),
+                                    float(min_rgb_level), None, None, None, bool(return_depth), 0.0, sh_rest,
+                                    3 if raw_params else 0, False, hints)
+    else:
+        out = _RenderSubposes.apply(means3d, scales, quats, opacities, sh, viewmats.reshape(B * S * R, 4, 4), background,
+                                    B * S, R, fx, fy, cx, cy, H, W, sh_degree, antialiased, glob_scale, clip_thresh,
+                                    xy_grad_out, bool(return_alpha), float(gamma), float(min_rgb_level), None, None, None,
+                                    bool(return_depth), 0.0, sh_rest, 3 if raw_params else 0, False, hints, B)
+    rgb, alphas, radii, depth = out
+    rgb = rgb.reshape(B, H, W, 3)
+    alphas = alphas.reshape(B, S, H, W) if alphas is not None else None
+    radii = radii.reshape(B, S * R, N)
+    if return_depth:
+        return rgb, alphas, radii, depth.reshape(B, S, H, W)
+    return rgb, alphas, radii
 
 
 # --------------------------------------------------------------------------- #

@@ -153,8 +153,13 @@ def train_step(model: SplatfactoDeblurModel, optimizers: Dict[str, torch.optim.O
                gt_image: Tensor, ssim_lambda: float = 0.2, allreduce: Optional[str] = None,
                gt_depth: Optional[Tensor] = None, depth_lambda: float = 0.0) -> Dict[str, float]:
     """One training iteration: render (HIP) -> loss -> backward (HIP) -> [DP gradient all-reduce] -> Adam.
+    camera / gt_image (/ gt_depth) may be lists: B cameras rendered as one batch (model.get_outputs_batch), the loss
+    the mean over the cameras of the per-image loss, on the autograd route.
     gt_depth [H,W,1] (scene units, 0 = no measurement) with depth_lambda > 0 adds depth_loss(out["depth"], gt_depth)
     to the loss, on either route (the depth map follows the resolution schedule: downscale_depth)."""
+    if isinstance(camera, (list, tuple)):
+        return _train_step_batch(model, optimizers, list(camera), list(gt_image), ssim_lambda, allreduce,
+                                 gt_depth, depth_lambda)
     model.train()
     for o in optimizers.values():
         o.zero_grad(set_to_none=True)
@@ -213,6 +218,50 @@ def train_step(model: SplatfactoDeblurModel, optimizers: Dict[str, torch.optim.O
     return {"loss": float(loss_v), "psnr": float("inf") if mse_v == 0 else -10.0 * math.log10(mse_v)}
 
 
+def _dp_allreduce(model: SplatfactoDeblurModel, allreduce: str) -> None:
+    from . import dp
+    dp.allreduce_gradients(list(model.gauss_params().values()), mode=allreduce, average=True)
+    small = [p for p in (model.background_param, model.pose_adjustment, model.velocity_adjustment) if p is not None]
+    for p in small:
+        if p.grad is None:
+            p.grad = torch.zeros_like(p)
+    dp.allreduce_dense_([p.grad for p in small], average=True)
+
+
+def _train_step_batch(model: SplatfactoDeblurModel, optimizers, cameras, gt_images, ssim_lambda, allreduce,
+                      gt_depths, depth_lambda) -> Dict[str, float]:
+    """train_step for B cameras: one get_outputs_batch, loss = mean over the cameras of train_step's per-image loss
+    (image loss + optional depth loss), one autograd backward, one optimizer step"""
+    if len(cameras) != len(gt_images) or not cameras:
+        raise ValueError("train_step needs as many images as cameras")
+    model.train()
+    for o in optimizers.values():
+        o.zero_grad(set_to_none=True)
+    d = model.downscale_factor()
+    gts = [downscale_image(g, d) for g in gt_images]
+    use_depth = gt_depths is not None and depth_lambda > 0
+    if use_depth:
+        gt_depths = [None if g is None else downscale_depth(g.to(gts[0].device, torch.float32), d) for g in gt_depths]
+    out = model.get_outputs_batch(cameras, return_depth=True) if use_depth else model.get_outputs_batch(cameras)
+    losses = []
+    for b in range(len(cameras)):
+        l_b = image_loss(out["rgb"][b], gts[b], ssim_lambda)
+        if use_depth and gt_depths[b] is not None:
+            l_b = l_b + depth_loss(out["depth"][b], gt_depths[b], depth_lambda)
+        losses.append(l_b)
+    loss = torch.stack([l.reshape(()) for l in losses]).mean()
+    if model.config.use_scale_regularization:
+        loss = loss + scale_regularization(model.scales)
+    loss.backward()
+    if allreduce is not None:
+        _dp_allreduce(model, allreduce)
+    optimizers_step(optimizers.values())
+    model.step += 1
+    mse = torch.stack([F.mse_loss(out["rgb"][b].detach().clamp(0, 1), gts[b].clamp(0, 1)) for b in range(len(cameras))]).mean()
+    loss_v, mse_v = torch.stack([loss.detach().reshape(()).float(), mse.float()]).tolist()
+    return {"loss": float(loss_v), "psnr": float("inf") if mse_v == 0 else -10.0 * math.log10(mse_v)}
+
+
 # --------------------------------------------------------------------------- #
 # whole-scene training / evaluation on a transforms.json dataset (the trainer-side callers of the hot path that the
 # end-to-end deblurring check needs; /root/reference/train.py:78-109 scores runs the same way: PSNR / SSIM of the
@@ -238,11 +287,17 @@ def eval_camera_step(model: SplatfactoDeblurModel, optimizers: Dict[str, torch.o
 
 
 @torch.no_grad()
-def evaluate(model: SplatfactoDeblurModel, cameras, images, indices) -> Dict[str, float]:
-    """mean PSNR / SSIM of the model's renders of `indices` against their images (sharp frames in the synthetic sets)"""
+def evaluate(model: SplatfactoDeblurModel, cameras, images, indices, batch_size: int = 1) -> Dict[str, float]:
+    """mean PSNR / SSIM of the model's renders of `indices` against their images (sharp frames in the synthetic sets).
+    batch_size > 1 renders up to that many cameras per call (model.get_outputs_for_cameras)"""
     ps, ss = [], []
-    for i in indices:
-        rgb = model.get_outputs_for_camera(cameras[i])["rgb"]
+    indices = list(indices)
+    if batch_size > 1:
+        rgbs = []
+        for k in range(0, len(indices), batch_size):
+            rgbs += list(model.get_outputs_for_cameras([cameras[i] for i in indices[k:k + batch_size]])["rgb"])
+    for n, i in enumerate(indices):
+        rgb = rgbs[n] if batch_size > 1 else model.get_outputs_for_camera(cameras[i])["rgb"]
         ps.append(psnr(rgb, images[i]))
         ss.append(float(ssim(rgb.clamp(0, 1), images[i]).item()))
     return {"psnr": sum(ps) / max(1, len(ps)), "ssim": sum(ss) / max(1, len(ss))}
@@ -250,11 +305,14 @@ def evaluate(model: SplatfactoDeblurModel, cameras, images, indices) -> Dict[str
 
 def train_scene(model: SplatfactoDeblurModel, scene, images, iterations: int, lr_scale: float = 1.0,
                 ssim_lambda: float = 0.2, optimize_eval_cameras: bool = False, eval_camera_every: int = 4,
-                densify=None, log_every: int = 0, seed: int = 0, depths=None, depth_lambda: float = 0.0) -> Dict:
+                densify=None, log_every: int = 0, seed: int = 0, depths=None, depth_lambda: float = 0.0,
+                batch_size: int = 1) -> Dict:
     """Train on scene.train_indices (one view per step, seeded shuffle), optionally refining the evaluation cameras
     in between; returns {'results': {psnr, ssim}, 'wall_clock_time_seconds', 'history'} like the reference's
     metrics.json (/root/reference/train.py:87-100, parse_outputs.py:58).  depths (optional): per-frame depth maps
-    [H,W,1] or None, indexed like images (data.load_depth); with depth_lambda > 0 every step adds the depth loss."""
+    [H,W,1] or None, indexed like images (data.load_depth); with depth_lambda > 0 every step adds the depth loss.
+    batch_size > 1: every step takes that many views of the shuffle (fewer at the end of a pass) as one batch
+    (train_step with lists), and the evaluation renders in batches of that size."""
     import time
     optimizers = make_optimizers(model, lr_scale)
     g = torch.Generator().manual_seed(seed)
@@ -275,9 +333,16 @@ def train_scene(model: SplatfactoDeblurModel, scene, images, iterations: int, lr
     for it in range(1, iterations + 1):
         if not order:
             order = [scene.train_indices[j] for j in torch.randperm(len(scene.train_indices), generator=g).tolist()]
-        i = order.pop()
-        gd = depths[i] if depths is not None else None
-        h = train_step(model, optimizers, scene.cameras[i], images[i], ssim_lambda, gt_depth=gd, depth_lambda=depth_lambda)
+        if batch_size > 1:
+            ids = [order.pop() for _ in range(min(batch_size, len(order)))]
+            gd = [depths[i] for i in ids] if depths is not None else None
+            h = train_step(model, optimizers, [scene.cameras[i] for i in ids], [images[i] for i in ids], ssim_lambda,
+                           gt_depth=gd, depth_lambda=depth_lambda)
+        else:
+            i = order.pop()
+            gd = depths[i] if depths is not None else None
+            h = train_step(model, optimizers, scene.cameras[i], images[i], ssim_lambda, gt_depth=gd,
+                           depth_lambda=depth_lambda)
         if densify is not None:
             from . import densify as D
             D.step_callback(model, optimizers, state, it, densify)
@@ -290,5 +355,5 @@ def train_scene(model: SplatfactoDeblurModel, scene, images, iterations: int, lr
     if model.means.is_cuda:
         torch.cuda.synchronize()
     wall = time.time() - t0
-    res = evaluate(model, scene.cameras, images, scene.eval_indices)
+    res = evaluate(model, scene.cameras, images, scene.eval_indices, batch_size=batch_size)
     return {"results": res, "wall_clock_time_seconds": wall, "history": history}

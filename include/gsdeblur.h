@@ -138,7 +138,10 @@ int gs_project_fused_bwd(int N, int P, const float* means3d, const float* scales
                                           gradient outputs and v_xy_sum itself — hand over uninitialised buffers; + 64:
                                           v_records[.., 11] holds d loss / d camera-space depth (record float 9, from
                                           gs_frame_backward_depth) and is chained to the means and the view matrices
-                                          (gs_project_pixvel_bwd: the mid-exposure view matrix only, no twist term)*/,
+                                          (gs_project_pixvel_bwd: the mid-exposure view matrix only, no twist term);
+                                          + 128 | (B << 8), B <= 256 dividing P (gs_project_fused_bwd, needs touched):
+                                          v_xy_sum is [B,N,2] — row b = the sum over sub-poses [b*P/B, (b+1)*P/B)
+                                          in sub-pose order, every row written (a frame of B cameras)*/,
                          const float* sh_rest, int param_flags /*both as in gs_project_fused_fwd: the gradients returned
                                           are those of what was handed in (d/d log-scale, d/d logit)*/,
                          float* v_sh_rest /*[N*(K_stride-1)*3] iff sh_rest != NULL (v_sh is then [N*3])*/,
@@ -499,6 +502,14 @@ int gs_combine_bwd(int S, long long n, const float* samples, float gamma, float 
 /* the sample-independent factor of gs_combine_bwd: scale[i] = (1/S) * out[i]^(1-gamma)/gamma * v_out[i] */
 int gs_combine_bwd_scale(int S, long long n, float gamma, const float* out, const float* v_out,
                          float* scale /*n*/, void* stream);
+/* the three calls above for B cameras in ONE launch: samples / v_samples [B*S*n] (camera b's S sample images
+ * contiguous), out / v_out / scale [B*n]; camera b's rows are bit-identical to the single-camera call on its slice */
+int gs_combine_fwd_batched(int B, int S, long long n, const float* samples, float gamma, float min_level,
+                           float* out, void* stream);
+int gs_combine_bwd_batched(int B, int S, long long n, const float* samples, float gamma, float min_level,
+                           const float* out, const float* v_out, float* v_samples, void* stream);
+int gs_combine_bwd_scale_batched(int B, int S, long long n, float gamma, const float* out, const float* v_out,
+                                 float* scale, void* stream);
 
 /* ---- data-parallel gradient exchange (no reference counterpart: the reference is single-GPU,
  *      train.py:114-122 passes no device / world-size flags) -------------------------------------------------
@@ -585,6 +596,11 @@ typedef struct gs_frame_desc {
   const struct gs_project_inputs* lazy_records;   /* NULL, or (the projection ran with defer_color bit 4: `records` holds
                                 nothing yet) what it was called with: every issued slice first projects the records of
                                 its own pairs (gs_slice_project_records).  SE(3) sub-poses only (pix_vel == NULL) */
+  int cameras;               /* 0 or 1: one camera.  B > 1 (SE(3) sub-poses, B divides S): the frame holds B cameras —
+                                camera b owns sample images [b*S/B, (b+1)*S/B) and sub-poses [b*P/B, (b+1)*P/B), S stays
+                                the number of sample images; out_combined is then [B,H,W,3] (gs_combine_fwd_batched) and
+                                the backward's cmb_scale [B,H,W,3] (gs_combine_bwd_scale_batched).  The 32-bit pixel
+                                offsets keep S*H*W < 2^30 for the whole batch */
 } gs_frame_desc;
 typedef struct gs_frame_slice {
   long long I;               /* capacity of the slice's lists (its ranks' bounding-box pairs); real count on the device */
@@ -605,6 +621,7 @@ typedef struct gs_frame_state {
   long long arena_used;      /* bytes of the arena the forward occupies (kept alive until the backward ran) */
   long long arena_required;  /* on GS_ERR_WORKSPACE (3): an arena size that holds the frame as far as it is known */
   gs_frame_slice slice[GS_FRAME_MAX_SLICES];
+  int cameras;               /* copied from the descriptor (1 for 0) */
 } gs_frame_state;
 /* records / depth_keys (consumed) / num_tiles_hit: outputs of gs_project_fused_fwd or gs_project_pixvel_fwd;
  * band_tile_done [P*T] u8: initial done mask of a rolling-shutter frame (R > 1; NULL otherwise); color_*: deferred SH
