@@ -91,6 +91,9 @@ _SIGS = {
     "gs_frame_profile_read": [_I, _P, _P],
     "gs_image_loss_fwd_bwd": [_I, _I, _P, _P, _F, _P, _P, _P, _L, _P],
     "gs_adam_step": [_I, _P, _P, _P, _P, _P, _P, ctypes.c_double, ctypes.c_double, ctypes.c_double, _I, _P],
+    "gs_adam_step_rows": [_I, _I, _P, _P, _P, _P, _P, _P, _P, ctypes.c_double, ctypes.c_double, ctypes.c_double, _I,
+                          _P, _L, _P],
+    "gs_visible_rows": [_I, _I, _P, _P, _P],
 }
 _SIGS_LL = {
     "gs_scan_workspace_bytes": [_L],
@@ -100,6 +103,7 @@ _SIGS_LL = {
     "gs_depth_select_workspace_bytes": [_I],
     "gs_project_pose_scratch_bytes": [_I, _I, _I],
     "gs_image_loss_workspace_bytes": [_I, _I],
+    "gs_adam_step_rows_workspace_bytes": [_I],
     "gs_frame_backward_bytes": [_P],
 }
 

@@ -341,3 +341,232 @@ GS_EXPORT int gs_adam_step(int count, float* const* params, const float* const* 
   hipLaunchKernelGGL(adam_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
   return gs_launch_status();
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// row-masked ("selective") multi-tensor Adam: gs_adam_step's arithmetic on the rows r with mask[r] != 0 only.
+// The tensors share N rows, tensor t has width[t] floats per row (3, 3, 4, 1, 3, 45 for the Gaussian groups at SH
+// degree 3: rows do not align to float4).  Work scales with the selected rows, not with N:
+//   K1 rows_count_kernel    per 4096-row chunk, how many rows are selected                   (reads N bytes)
+//   K2 rows_scan_kernel     ONE block: exclusive scan of the chunk counts + the grand total (kept on the device)
+//   K3 rows_compact_kernel  per chunk, the selected row ids in ascending order (wave ballot + block prefix)
+//   K4 adam_rows_kernel     grid-stride over the (selected row, column) pairs of each tensor in turn, up to the
+//                           device-side total: adjacent lanes take adjacent columns of a row
+// No atomics (every element has exactly one writer), no host read-back, no launch sized by the selected count.
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int kRowsChunk = 4096;            // rows per block of K1 / K3: 16 passes of 256
+constexpr int kRowsMaxWidth = 64;
+constexpr int kRowsUnroll = 4;              // independent elements in flight per thread and pass of K4
+
+struct AdamRowsArgs {
+  float* p[kAdamMaxTensors];
+  const float* g[kAdamMaxTensors];
+  float* m[kAdamMaxTensors];
+  float* v[kAdamMaxTensors];
+  int width[kAdamMaxTensors];
+  float step_size[kAdamMaxTensors];         // lr / bias_correction1, as gs_adam_step
+  int count, n_rows_all;                    // n_rows_all = N
+  float beta1, beta2, omb1, omb2, eps, inv_sqrt_bc2;
+};
+
+__device__ __forceinline__ int block_sum_256(int x, int* red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = x;
+  __syncthreads();
+  const int s = (red[0] + red[1]) + (red[2] + red[3]);
+  __syncthreads();
+  return s;
+}
+
+__global__ __launch_bounds__(256) void rows_count_kernel(int N, const unsigned char* __restrict__ mask,
+                                                         int* __restrict__ chunk_count) {
+  __shared__ int red[4];
+  const long long r0 = (long long)blockIdx.x * kRowsChunk;
+  int c = 0;
+  for (int i = threadIdx.x; i < kRowsChunk; i += 256) {
+    const long long r = r0 + i;
+    c += (r < N && mask[r] != 0) ? 1 : 0;
+  }
+  c = block_sum_256(c, red);
+  if (threadIdx.x == 0) chunk_count[blockIdx.x] = c;
+}
+
+// one block: chunk_off[b] = sum of chunk_count[0 .. b), *total = the sum of all
+__global__ __launch_bounds__(256) void rows_scan_kernel(int n_chunks, const int* __restrict__ chunk_count,
+                                                        int* __restrict__ chunk_off, int* __restrict__ total) {
+  __shared__ int wsum[4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int carry = 0;
+  for (int b0 = 0; b0 < n_chunks; b0 += 256) {
+    const int b = b0 + threadIdx.x;
+    const int x = b < n_chunks ? chunk_count[b] : 0;
+    int inc = x;                                            // wave-inclusive scan
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int y = __shfl_up(inc, o);
+      if (lane >= o) inc += y;
+    }
+    if (lane == 63) wsum[wave] = inc;
+    __syncthreads();
+    int before = carry;
+    for (int w = 0; w < wave; ++w) before += wsum[w];
+    if (b < n_chunks) chunk_off[b] = before + inc - x;
+    carry += (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) *total = carry;
+}
+
+__global__ __launch_bounds__(256) void rows_compact_kernel(int N, const unsigned char* __restrict__ mask,
+                                                           const int* __restrict__ chunk_off, int* __restrict__ rows) {
+  __shared__ int wcnt[4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const long long r0 = (long long)blockIdx.x * kRowsChunk;
+  int base = chunk_off[blockIdx.x];
+  for (int i = 0; i < kRowsChunk; i += 256) {
+    const long long r = r0 + i + threadIdx.x;
+    const bool sel = r < N && mask[r] != 0;
+    const unsigned long long b = __ballot(sel);
+    const int below = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, 0u));
+    if (lane == 0) wcnt[wave] = __popcll(b);
+    __syncthreads();
+    int off = base;
+    for (int w = 0; w < wave; ++w) off += wcnt[w];
+    if (sel) rows[off + below] = (int)r;
+    base += (wcnt[0] + wcnt[1]) + (wcnt[2] + wcnt[3]);
+    __syncthreads();
+  }
+}
+
+// adam_one's arithmetic with the roundings gs_adam_step's code has on gfx950, written out so that the selected
+// elements come out bit-identical to it: its float4 body forms v as fma(v, b2, g * (omb2 g)), its scalar tail (the
+// last numel % 4 elements of a tensor) as fma(g, omb2 g, v * b2); m, the denominator and p are the same in both.
+__device__ __forceinline__ void adam_one_as_dense(float& p, float g, float& m, float& v, float omb1, float b2,
+                                                  float omb2, float eps, float isbc2, float step, bool tail) {
+#pragma clang fp contract(off)
+  const float og = omb2 * g;
+  v = tail ? __builtin_fmaf(g, og, v * b2) : __builtin_fmaf(v, b2, g * og);
+  m = __builtin_fmaf(g - m, omb1, m);
+  const float denom = __builtin_fmaf(sqrtf(v), isbc2, eps);
+  p = __builtin_fmaf(-step, m / denom, p);
+}
+
+// one tensor's (row, column) pairs; I = the index type (32-bit whenever cnt * width fits, the common case)
+template <typename I>
+__device__ __forceinline__ void adam_rows_tensor(const AdamRowsArgs& a, int t, I total, I first, I stride,
+                                                 const int* __restrict__ rows) {
+  float* __restrict__ P = a.p[t];
+  const float* __restrict__ G = a.g[t];
+  float* __restrict__ M = a.m[t];
+  float* __restrict__ V = a.v[t];
+  const I w = (I)a.width[t];
+  const float step = a.step_size[t];
+  const size_t tail_from = (size_t)a.n_rows_all * (size_t)a.width[t] & ~(size_t)3;   // gs_adam_step's scalar tail
+  for (I e0 = first; e0 < total; e0 += stride * kRowsUnroll) {
+    size_t off[kRowsUnroll];
+    float p[kRowsUnroll], g[kRowsUnroll], m[kRowsUnroll], v[kRowsUnroll];
+#pragma unroll
+    for (int k = 0; k < kRowsUnroll; ++k) {
+      const I e = e0 + (I)k * stride;
+      off[k] = 0;
+      if (e < total) {
+        const I r = e / w;
+        off[k] = (size_t)rows[r] * (size_t)w + (size_t)(e - r * w);
+        p[k] = P[off[k]]; g[k] = G[off[k]]; m[k] = M[off[k]]; v[k] = V[off[k]];
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < kRowsUnroll; ++k) {
+      if (e0 + (I)k * stride < total) {
+        adam_one_as_dense(p[k], g[k], m[k], v[k], a.omb1, a.beta2, a.omb2, a.eps, a.inv_sqrt_bc2, step,
+                          off[k] >= tail_from);
+        P[off[k]] = p[k]; M[off[k]] = m[k]; V[off[k]] = v[k];
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void adam_rows_kernel(AdamRowsArgs a, const int* __restrict__ rows,
+                                                        const int* __restrict__ n_rows) {
+  const unsigned long long cnt = (unsigned long long)(unsigned)*n_rows;
+  const unsigned long long first = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
+  const unsigned long long stride = (unsigned long long)gridDim.x * 256;
+  for (int t = 0; t < a.count; ++t) {
+    const unsigned long long total = cnt * (unsigned long long)a.width[t];
+    if (total + stride * kRowsUnroll < (1ull << 32))
+      adam_rows_tensor<unsigned>(a, t, (unsigned)total, (unsigned)first, (unsigned)stride, rows);
+    else
+      adam_rows_tensor<unsigned long long>(a, t, total, first, stride, rows);
+  }
+}
+
+// mask[r] = any_p radii[p * N + r] > 0
+__global__ __launch_bounds__(256) void visible_rows_kernel(int M, int N, const int* __restrict__ radii,
+                                                           unsigned char* __restrict__ mask) {
+  const long long stride = (long long)gridDim.x * 256;
+  for (long long r = (long long)blockIdx.x * 256 + threadIdx.x; r < N; r += stride) {
+    unsigned char vis = 0;
+    for (int p = 0; p < M && !vis; ++p) vis = radii[(size_t)p * N + r] > 0 ? 1 : 0;
+    mask[r] = vis;
+  }
+}
+
+static inline long long rows_chunks(int N) { return ((long long)N + kRowsChunk - 1) / kRowsChunk; }
+
+// workspace: row ids [N] | chunk counts [chunks] | chunk offsets [chunks] | total [1]   (int32)
+GS_EXPORT long long gs_adam_step_rows_workspace_bytes(int N) {
+  if (N <= 0) return 0;
+  return ((long long)N + 2 * rows_chunks(N) + 1) * 4 + 256;
+}
+
+// gs_adam_step on the rows with mask[r] != 0: see include/gsdeblur.h
+GS_EXPORT int gs_adam_step_rows(int count, int N, const unsigned char* mask, float* const* params,
+                                const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                                const int* widths, const float* lr, double beta1, double beta2, double eps, int step,
+                                void* ws, long long ws_bytes, void* stream) {
+  if (count <= 0 || count > kAdamMaxTensors || N < 0 || step <= 0 || !params || !grads || !exp_avg || !exp_avg_sq ||
+      !widths || !lr)
+    return GS_ERR_INVALID;
+  AdamRowsArgs a;
+  int wmax = 0;
+  for (int t = 0; t < count; ++t) {
+    if (widths[t] < 1 || widths[t] > kRowsMaxWidth) return GS_ERR_INVALID;
+    if (N > 0 && (!params[t] || !grads[t] || !exp_avg[t] || !exp_avg_sq[t])) return GS_ERR_INVALID;
+    wmax = widths[t] > wmax ? widths[t] : wmax;
+  }
+  if (N == 0) return GS_OK;
+  if (!mask) return GS_ERR_INVALID;
+  if (!ws || ws_bytes < gs_adam_step_rows_workspace_bytes(N)) return GS_ERR_WORKSPACE;
+  const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
+  for (int t = 0; t < count; ++t) {
+    a.p[t] = params[t]; a.g[t] = grads[t]; a.m[t] = exp_avg[t]; a.v[t] = exp_avg_sq[t]; a.width[t] = widths[t];
+    a.step_size[t] = (float)((double)lr[t] / bc1);
+  }
+  a.count = count; a.n_rows_all = N; a.beta1 = (float)beta1; a.beta2 = (float)beta2; a.omb1 = (float)(1.0 - beta1);
+  a.omb2 = (float)(1.0 - beta2); a.eps = (float)eps; a.inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
+  const long long chunks = rows_chunks(N);
+  int* rows = reinterpret_cast<int*>(ws);
+  int* chunk_count = rows + N;
+  int* chunk_off = chunk_count + chunks;
+  int* total = chunk_off + chunks;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(rows_count_kernel, dim3((unsigned)chunks), dim3(256), 0, st, N, mask, chunk_count);
+  hipLaunchKernelGGL(rows_scan_kernel, dim3(1), dim3(256), 0, st, (int)chunks, chunk_count, chunk_off, total);
+  hipLaunchKernelGGL(rows_compact_kernel, dim3((unsigned)chunks), dim3(256), 0, st, N, mask, chunk_off, rows);
+  // grid from N (the host never learns the selected count): enough blocks for a fully selected step, at most 2048
+  const long long want = ((long long)N * wmax + 256LL * kRowsUnroll - 1) / (256LL * kRowsUnroll);
+  const unsigned blocks = (unsigned)(want < 1 ? 1 : (want > 2048 ? 2048 : want));
+  hipLaunchKernelGGL(adam_rows_kernel, dim3(blocks), dim3(256), 0, st, a, rows, total);
+  return gs_launch_status();
+}
+
+// mask[r] = 1 if radii[p * N + r] > 0 for any of the M planes, else 0
+GS_EXPORT int gs_visible_rows(int M, int N, const int* radii, unsigned char* mask, void* stream) {
+  if (M <= 0 || N < 0) return GS_ERR_INVALID;
+  if (N == 0) return GS_OK;
+  if (!radii || !mask) return GS_ERR_INVALID;
+  const long long want = ((long long)N + 255) / 256;
+  const unsigned blocks = (unsigned)(want > 4096 ? 4096 : want);
+  hipLaunchKernelGGL(visible_rows_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, M, N, radii, mask);
+  return gs_launch_status();
+}

@@ -392,3 +392,16 @@ def allreduce_dense_(tensors: Sequence[torch.Tensor], group: Optional[dist.Proce
         n = t.numel()
         t.copy_(flat[off:off + n].view_as(t))
         off += n
+
+
+def allreduce_mask_max_(mask: torch.Tensor, group: Optional[dist.ProcessGroup] = None,
+                        force: Optional[bool] = None) -> None:
+    """In-place MAX of a bool / uint8 row mask [N] over the ranks (N bytes): selective Adam's "visible" mask, which
+    each rank builds from its own views — without it the replicas would step different rows and drift apart."""
+    if mask.numel() == 0 or not dist.is_available() or not dist.is_initialized():
+        return
+    world = dist.get_world_size(group)
+    if world == 1 and not (FORCE if force is None else force):
+        return
+    m8 = mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+    dist.all_reduce(m8, op=dist.ReduceOp.MAX, group=group)

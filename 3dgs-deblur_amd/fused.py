@@ -10,7 +10,7 @@ tests use the torch implementations explicitly (train_step.image_loss / make_opt
 from __future__ import annotations
 
 import ctypes
-from typing import Dict, Iterable, List
+from typing import Dict, Iterable, List, Optional
 
 import torch
 from torch import Tensor
@@ -82,10 +82,13 @@ def image_loss(pred: Tensor, gt: Tensor, ssim_lambda: float = 0.2, return_parts:
 
 # --------------------------------------------------------------------------- #
 class HipAdam(torch.optim.Optimizer):
-    """torch.optim.Adam (no weight decay, no amsgrad) through gs_adam_step; state keys as torch's."""
+    """torch.optim.Adam (no weight decay, no amsgrad) through gs_adam_step; state keys as torch's.
+    selective=True marks the optimizer of a Gaussian group for selective Adam (adam_step_all's row_mask)."""
 
-    def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8):
+    def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, selective: bool = False):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps))
+        # selective: train_step builds a row mask for the step and adam_step_all updates only the selected rows
+        self.selective = bool(selective)
 
     def _gather(self, items: List[tuple]) -> None:
         for group in self.param_groups:
@@ -136,14 +139,80 @@ def _launch(items: List[tuple]) -> None:
                                           _stream()), "adam_step")
 
 
+def _launch_rows(items: List[tuple], mask: Tensor) -> None:
+    """gs_adam_step_rows: the rows with mask[r] != 0 of tensors that share the leading dimension N = mask.numel();
+    tensors that share (betas, eps, step) go out in one launch of up to 8"""
+    if not items:
+        return
+    L = _lib.load()
+    N = int(mask.numel())
+    m8 = mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+    if m8.dtype != torch.uint8 or not m8.is_contiguous():
+        m8 = m8.to(torch.uint8).contiguous()
+    groups: Dict[tuple, List[tuple]] = {}
+    for it in items:
+        groups.setdefault((it[5], it[6], it[7], it[0].device), []).append(it)
+    for (betas, eps, step, dev), its in groups.items():
+        if m8.device != dev:
+            raise ValueError("row_mask must live on the parameters' device")
+        with torch.cuda.device(dev):
+            ws_bytes = L.gs_adam_step_rows_workspace_bytes(N)
+            ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+            for i in range(0, len(its), 8):
+                chunk = its[i:i + 8]
+                n = len(chunk)
+                vp = ctypes.c_void_p
+                P = (vp * n)(*[c[0].data_ptr() for c in chunk])
+                G = (vp * n)(*[c[1].data_ptr() for c in chunk])
+                M = (vp * n)(*[c[2].data_ptr() for c in chunk])
+                V = (vp * n)(*[c[3].data_ptr() for c in chunk])
+                W = (ctypes.c_int * n)(*[c[0].numel() // N if N else 1 for c in chunk])
+                LR = (ctypes.c_float * n)(*[c[4] for c in chunk])
+                _lib.check(L.gs_adam_step_rows(n, N, vp(m8.data_ptr()), P, G, M, V, W, LR, float(betas[0]),
+                                               float(betas[1]), float(eps), int(step), vp(ws.data_ptr()), ws_bytes,
+                                               _stream()), "adam_step_rows")
+
+
 @torch.no_grad()
-def adam_step_all(optimizers: Iterable[torch.optim.Optimizer]) -> None:
+def adam_step_all(optimizers: Iterable[torch.optim.Optimizer], row_mask: Optional[Tensor] = None) -> None:
     """One step of every optimizer: all HipAdam instances together in one multi-tensor launch (per distinct
-    betas / eps / step count), anything else through its own .step()."""
+    betas / eps / step count), anything else through its own .step().
+    row_mask (bool / uint8 [N], optional): selective Adam — the HipAdam parameters with leading dimension N (the
+    per-Gaussian groups) step only their rows with row_mask != 0 (gs_adam_step_rows: the other rows' parameter and
+    moments stay bit-unchanged); every other parameter (camera pose, velocity, background) steps densely as without a
+    mask.  The step counts advance as in a dense step: bias correction uses the optimizer's global step (gsplat)."""
     items: List[tuple] = []
     for o in optimizers:
         if isinstance(o, HipAdam):
             o._gather(items)
+        elif row_mask is not None and getattr(o, "selective", False):
+            o.step(row_mask)              # train_step.SelectiveAdam (the torch form)
         else:
             o.step()
-    _launch(items)
+    if row_mask is None:
+        _launch(items)
+        return
+    N = int(row_mask.numel())
+    rows = [it for it in items if it[0].dim() >= 1 and it[0].shape[0] == N]
+    dense = [it for it in items if not (it[0].dim() >= 1 and it[0].shape[0] == N)]
+    _launch(dense)
+    _launch_rows(rows, row_mask)
+
+
+def visible_rows(radii: Tensor) -> Tensor:
+    """gs_visible_rows: radii int32 [M, N] (the sub-pose planes of a step, cameras included) -> bool [N], True where
+    the row has radius > 0 in any plane (gsplat's visibility rule for selective Adam)"""
+    if not radii.is_cuda:
+        raise ValueError("radii must be a CUDA(HIP) tensor: the HIP path has no CPU fallback")
+    if radii.dtype != torch.int32 or radii.dim() != 2:
+        raise ValueError("radii must be int32 [M, N]")
+    radii = radii.contiguous()
+    M, N = int(radii.shape[0]), int(radii.shape[1])
+    mask = torch.empty(N, dtype=torch.uint8, device=radii.device)
+    if N == 0:
+        return mask.view(torch.bool)
+    L = _lib.load()
+    with torch.cuda.device(radii.device):
+        _lib.check(L.gs_visible_rows(M, N, ctypes.c_void_p(radii.data_ptr()), ctypes.c_void_p(mask.data_ptr()),
+                                     _stream()), "visible_rows")
+    return mask.view(torch.bool)

@@ -66,6 +66,12 @@ class SplatfactoDeblurConfig:
     pixel_velocity_lists: str = "per_sample"
     camera_optimizer: CameraOptimizerConfig = field(default_factory=CameraOptimizerConfig)
     camera_velocity_optimizer: CameraVelocityOptimizerConfig = field(default_factory=CameraVelocityOptimizerConfig)
+    # "adam": every Gaussian row steps every iteration (torch.optim.Adam); "selective_adam": only the rows the step's
+    # views reached (gsplat's SelectiveAdam) — the others keep parameter and both moments unchanged
+    optimizer: str = "adam"
+    # selective_adam's row mask: "visible" = radii > 0 in any sub-pose of any camera of the step (gsplat's rule);
+    # "touched" = any non-zero gradient in any Gaussian parameter (what the compositor reached)
+    selective_mask: str = "visible"
 
 
 @dataclass

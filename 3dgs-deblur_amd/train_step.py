@@ -10,6 +10,7 @@ device and the HIP side raises when the library is missing.
 """
 from __future__ import annotations
 
+import functools
 import math
 import os
 from typing import Dict, Optional
@@ -102,20 +103,82 @@ def scale_regularization(log_scales: Tensor, max_gauss_ratio: float = 10.0) -> T
     return 0.1 * (torch.maximum(ratio, r) - r).mean()
 
 
+class SelectiveAdam(torch.optim.Optimizer):
+    """Selective ("visibility-masked") Adam in plain torch: gsplat's SelectiveAdam / Taming-3DGS's sparse optimizer.
+    step(row_mask) runs torch.optim.Adam's update (no weight decay, no amsgrad; state keys and the tensor step count
+    as torch's) on the rows r with row_mask[r] only, for every parameter whose leading dimension is row_mask's length;
+    the other rows keep parameter, exp_avg and exp_avg_sq unchanged and their gradient is ignored.  The step count
+    advances every step and bias correction uses it (gsplat's rule: no per-row step count).  row_mask=None is a dense
+    torch.optim.Adam step.  The CPU / A/B form of fused.adam_step_all(row_mask=...) and its test oracle."""
+    selective = True
+
+    def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8):
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps))
+
+    @torch.no_grad()
+    def step(self, row_mask: Optional[Tensor] = None, closure=None):
+        for group in self.param_groups:
+            beta1, beta2 = group["betas"]
+            lr, eps = group["lr"], group["eps"]
+            for p in group["params"]:
+                if p.grad is None:
+                    continue
+                st = self.state[p]
+                if not st:
+                    st["step"] = torch.tensor(0.0)
+                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                st["step"] += 1
+                step = float(st["step"])
+                bias_correction1 = 1 - beta1 ** step
+                bias_correction2 = 1 - beta2 ** step
+                step_size = lr / bias_correction1
+                bias_correction2_sqrt = bias_correction2 ** 0.5
+                exp_avg, exp_avg_sq = st["exp_avg"], st["exp_avg_sq"]
+                idx = None
+                if row_mask is not None and p.dim() >= 1 and p.shape[0] == row_mask.numel():
+                    idx = row_mask.to(device=p.device, dtype=torch.bool).nonzero().reshape(-1)
+                if idx is None:
+                    q, g, m, v = p, p.grad, exp_avg, exp_avg_sq
+                else:
+                    q, g, m, v = (t.index_select(0, idx) for t in (p, p.grad, exp_avg, exp_avg_sq))
+                m.lerp_(g, 1 - beta1)
+                v.mul_(beta2).addcmul_(g, g, value=1 - beta2)
+                denom = (v.sqrt() / bias_correction2_sqrt).add_(eps)
+                q.addcdiv_(m, denom, value=-step_size)
+                if idx is not None:
+                    p.index_copy_(0, idx, q)
+                    exp_avg.index_copy_(0, idx, m)
+                    exp_avg_sq.index_copy_(0, idx, v)
+
+
+OPTIMIZERS = ("adam", "selective_adam")
+SELECTIVE_MASKS = ("visible", "touched")
+
+
 def make_optimizers(model: SplatfactoDeblurModel, lr_scale: float = 1.0,
-                    fused: Optional[bool] = None) -> Dict[str, torch.optim.Optimizer]:
+                    fused: Optional[bool] = None, optimizer: Optional[str] = None) -> Dict[str, torch.optim.Optimizer]:
     """One Adam per parameter group with splatfacto's default learning rates.  fused (default: the parameters live on
     a GPU): HipAdam — same update rule and state layout as torch.optim.Adam, stepped by ONE multi-tensor HIP launch
-    (`optimizers_step`); False: torch.optim.Adam (CPU tensors, A/B)."""
+    (`optimizers_step`); False: torch.optim.Adam (CPU tensors, A/B).
+    optimizer (default: model.config.optimizer): "adam", or "selective_adam" — the six Gaussian groups then step only
+    the rows of train_step's row mask (model.config.selective_mask): HipAdam(selective=True) through
+    gs_adam_step_rows, or SelectiveAdam when not fused.  Pose, velocity and background optimizers stay dense."""
     lrs = {"means": 1.6e-4, "scales": 5e-3, "quats": 1e-3, "opacities": 5e-2, "features_dc": 2.5e-3,
            "features_rest": 2.5e-3 / 20}
+    optimizer = model.config.optimizer if optimizer is None else optimizer
+    if optimizer not in OPTIMIZERS:
+        raise ValueError(f"unknown optimizer {optimizer!r} (one of {OPTIMIZERS})")
+    selective = optimizer == "selective_adam"
     if fused is None:
         fused = model.means.is_cuda and not TORCH_TRAIN
     if fused:
         from .fused import HipAdam as Adam
+        GaussAdam = functools.partial(Adam, selective=True) if selective else Adam
     else:
         Adam = torch.optim.Adam
-    opts = {k: Adam([p], lr=lrs[k] * lr_scale, eps=1e-15) for k, p in model.gauss_params().items()}
+        GaussAdam = SelectiveAdam if selective else Adam
+    opts = {k: GaussAdam([p], lr=lrs[k] * lr_scale, eps=1e-15) for k, p in model.gauss_params().items()}
     if model.pose_adjustment is not None:
         opts["camera_opt"] = Adam([model.pose_adjustment], lr=1e-4 * lr_scale, eps=1e-15)
     if model.velocity_adjustment is not None:
@@ -125,15 +188,60 @@ def make_optimizers(model: SplatfactoDeblurModel, lr_scale: float = 1.0,
     return opts
 
 
-def optimizers_step(optimizers) -> None:
-    """step every optimizer of the iteration; HipAdam instances share one multi-tensor launch"""
+def optimizers_step(optimizers, row_mask: Optional[Tensor] = None) -> None:
+    """step every optimizer of the iteration; HipAdam instances share one multi-tensor launch.  row_mask (bool [N]):
+    selective Adam — the per-Gaussian groups step only the selected rows (fused.adam_step_all / SelectiveAdam)"""
     opts = list(optimizers)
     if any(type(o).__name__ == "HipAdam" for o in opts):
         from .fused import adam_step_all
-        adam_step_all(opts)
+        if row_mask is None:
+            adam_step_all(opts)
+        else:
+            adam_step_all(opts, row_mask=row_mask)
     else:
         for o in opts:
-            o.step()
+            if row_mask is not None and getattr(o, "selective", False):
+                o.step(row_mask)
+            else:
+                o.step()
+
+
+def selection_mask(model: SplatfactoDeblurModel, optimizers, allreduce: Optional[str] = None) -> Optional[Tensor]:
+    """The row mask of a selective-Adam step (bool [N]), or None when no optimizer of the step is selective (plain
+    Adam: nothing is built).  Call after the backward and after any DP gradient exchange.
+    model.config.selective_mask "visible": rows with radii > 0 in any sub-pose of any camera of the step (model.radii;
+    gs_visible_rows), made identical on every rank by a MAX all-reduce under data parallelism; "touched": rows with
+    any non-zero gradient in any Gaussian parameter (gs_dp_row_mask), read from the exchanged gradients, hence
+    identical on every rank with no collective of its own."""
+    if not any(getattr(o, "selective", False) for o in optimizers):
+        return None
+    kind = model.config.selective_mask
+    N = model.num_points
+    dev = model.means.device
+    if kind == "touched":
+        grads = [p.grad.contiguous() for p in model.gauss_params().values() if p.grad is not None]
+        if N == 0 or not grads:
+            return torch.zeros(N, dtype=torch.bool, device=dev)
+        from .dp import _RowOps
+        return _RowOps(grads).row_mask()
+    if kind != "visible":
+        raise ValueError(f"unknown selective_mask {kind!r} (one of {SELECTIVE_MASKS})")
+    radii = model.radii
+    if radii is None:
+        raise RuntimeError("selective_mask='visible' needs the step's radii (model.radii): render before the step")
+    planes = [r.reshape(-1, r.shape[-1]) for r in (radii if isinstance(radii, (list, tuple)) else [radii])]
+    if any(r.shape[-1] != N for r in planes):
+        raise RuntimeError(f"model.radii has {planes[0].shape[-1]} rows, the model {N}: radii of an earlier step")
+    planes = planes[0] if len(planes) == 1 else torch.cat(planes)
+    if planes.is_cuda:
+        from .fused import visible_rows
+        mask = visible_rows(planes.to(torch.int32))
+    else:
+        mask = (planes > 0).any(dim=0)
+    if allreduce is not None:
+        from . import dp
+        dp.allreduce_mask_max_(mask)
+    return mask
 
 
 # GSD_TRAIN_AUTOGRAD=1: train_step goes through get_outputs + torch.autograd instead of the one-call route (A/B, tests)
@@ -210,7 +318,7 @@ def train_step(model: SplatfactoDeblurModel, optimizers: Dict[str, torch.optim.O
             if p.grad is None:
                 p.grad = torch.zeros_like(p)
         dp.allreduce_dense_([p.grad for p in small], average=True)
-    optimizers_step(optimizers.values())
+    optimizers_step(optimizers.values(), row_mask=selection_mask(model, optimizers.values(), allreduce))
     model.step += 1
     # ONE read-back for the step's two log values (each .item() is a stream synchronisation)
     mse = F.mse_loss(rgb.clamp(0, 1), gt_image.clamp(0, 1))
@@ -255,7 +363,7 @@ def _train_step_batch(model: SplatfactoDeblurModel, optimizers, cameras, gt_imag
     loss.backward()
     if allreduce is not None:
         _dp_allreduce(model, allreduce)
-    optimizers_step(optimizers.values())
+    optimizers_step(optimizers.values(), row_mask=selection_mask(model, optimizers.values(), allreduce))
     model.step += 1
     mse = torch.stack([F.mse_loss(out["rgb"][b].detach().clamp(0, 1), gts[b].clamp(0, 1)) for b in range(len(cameras))]).mean()
     loss_v, mse_v = torch.stack([loss.detach().reshape(()).float(), mse.float()]).tolist()
@@ -306,15 +414,16 @@ def evaluate(model: SplatfactoDeblurModel, cameras, images, indices, batch_size:
 def train_scene(model: SplatfactoDeblurModel, scene, images, iterations: int, lr_scale: float = 1.0,
                 ssim_lambda: float = 0.2, optimize_eval_cameras: bool = False, eval_camera_every: int = 4,
                 densify=None, log_every: int = 0, seed: int = 0, depths=None, depth_lambda: float = 0.0,
-                batch_size: int = 1) -> Dict:
+                batch_size: int = 1, optimizer: Optional[str] = None) -> Dict:
     """Train on scene.train_indices (one view per step, seeded shuffle), optionally refining the evaluation cameras
     in between; returns {'results': {psnr, ssim}, 'wall_clock_time_seconds', 'history'} like the reference's
     metrics.json (/root/reference/train.py:87-100, parse_outputs.py:58).  depths (optional): per-frame depth maps
     [H,W,1] or None, indexed like images (data.load_depth); with depth_lambda > 0 every step adds the depth loss.
     batch_size > 1: every step takes that many views of the shuffle (fewer at the end of a pass) as one batch
-    (train_step with lists), and the evaluation renders in batches of that size."""
+    (train_step with lists), and the evaluation renders in batches of that size.  optimizer: make_optimizers' choice
+    ("adam" / "selective_adam"; default model.config.optimizer)."""
     import time
-    optimizers = make_optimizers(model, lr_scale)
+    optimizers = make_optimizers(model, lr_scale, optimizer=optimizer)
     g = torch.Generator().manual_seed(seed)
     order = []
     history = []

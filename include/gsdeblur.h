@@ -681,6 +681,21 @@ int gs_image_loss_fwd_bwd(int img_height, int img_width, const float* pred, cons
 int gs_adam_step(int count, float* const* params, const float* const* grads, float* const* exp_avg,
                  float* const* exp_avg_sq, const long long* numel, const float* lr, double beta1, double beta2, double eps,
                  int step, void* stream);
+/* Adam on the rows r of N with mask[r] != 0 only ("selective" Adam: gsplat's SelectiveAdam, Taming-3DGS's sparse
+ * optimizer); tensors share N rows, tensor t has widths[t] (1 .. 64) floats per row; count <= 8; params / grads /
+ * exp_avg / exp_avg_sq / widths / lr: HOST arrays (device pointers in the first four).
+ * Masked-off rows: parameter, exp_avg and exp_avg_sq are not written (bit-unchanged), the gradient is ignored.
+ * Selected elements get exactly gs_adam_step's arithmetic and roundings (same step / bias-correction scalars):
+ * bit-identical to what gs_adam_step writes for the same inputs.
+ * The selected rows are compacted on the device (prefix sum), so the work scales with their number and nothing is
+ * read back; ws: gs_adam_step_rows_workspace_bytes(N) bytes of device scratch.  N == 0 is a no-op. */
+int gs_adam_step_rows(int count, int N, const unsigned char* mask /*N*/, float* const* params,
+                      const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                      const int* widths, const float* lr, double beta1, double beta2, double eps, int step,
+                      void* ws, long long ws_bytes, void* stream);
+long long gs_adam_step_rows_workspace_bytes(int N);
+/* mask[r] = 1 if radii[p*N + r] > 0 for any of the M planes, else 0 (gsplat's visibility rule); radii int32 [M*N]. */
+int gs_visible_rows(int M, int N, const int* radii, unsigned char* mask, void* stream);
 
 #ifdef __cplusplus
 }

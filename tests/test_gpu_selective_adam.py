@@ -1,0 +1,301 @@
+"""Selective Adam on the GPU: gs_adam_step_rows against a float64 reference and bit for bit against the dense
+gs_adam_step on the selected rows (masked-off rows and the gradients untouched), gs_visible_rows against
+(radii > 0).any(0), and train_step with optimizer="selective_adam" under both masks on the one-call and the batched
+route, right after a densification, and over a short end-to-end training run."""
+import ctypes
+
+import pytest
+import torch
+
+from test_gpu_batch import _scene, _views
+
+pytestmark = pytest.mark.gpu
+
+WIDTHS = [1, 3, 4, 45, 64]
+LR = [1e-3, 5e-3, 2.5e-3, 5e-2, 1.25e-4]
+B1, B2, EPS = 0.9, 0.999, 1e-15
+
+
+def _tensors(N, widths, dev, seed):
+    g = torch.Generator(device=dev).manual_seed(seed)
+    out = []
+    for w in widths:
+        p = torch.randn(N, w, device=dev, generator=g)
+        gr = torch.randn(N, w, device=dev, generator=g) * 0.1
+        gr[torch.rand(N, w, device=dev, generator=g) < 0.1] = 0.0
+        m = torch.randn(N, w, device=dev, generator=g) * 0.01
+        v = torch.rand(N, w, device=dev, generator=g) * 1e-3
+        out.append([p, gr, m, v])
+    return out
+
+
+def _mask(N, kind, dev, seed):
+    if kind == "empty":
+        return torch.zeros(N, dtype=torch.bool, device=dev)
+    if kind == "full":
+        return torch.ones(N, dtype=torch.bool, device=dev)
+    g = torch.Generator(device=dev).manual_seed(seed + 1)
+    return torch.rand(N, device=dev, generator=g) < {"0.5%": 0.005, "50%": 0.5}[kind]
+
+
+def _call(L, fn, ts, N, mask, step, widths):
+    n = len(ts)
+    vp = ctypes.c_void_p
+    P = (vp * n)(*[t[0].data_ptr() for t in ts])
+    G = (vp * n)(*[t[1].data_ptr() for t in ts])
+    M = (vp * n)(*[t[2].data_ptr() for t in ts])
+    V = (vp * n)(*[t[3].data_ptr() for t in ts])
+    LRa = (ctypes.c_float * n)(*LR[:n])
+    stream = vp(torch.cuda.current_stream().cuda_stream)
+    if fn == "dense":
+        NE = (ctypes.c_longlong * n)(*[t[0].numel() for t in ts])
+        return L.gs_adam_step(n, P, G, M, V, NE, LRa, B1, B2, EPS, step, stream)
+    W = (ctypes.c_int * n)(*widths)
+    ws_bytes = L.gs_adam_step_rows_workspace_bytes(N)
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=mask.device)
+    return L.gs_adam_step_rows(n, N, vp(mask.view(torch.uint8).data_ptr()), P, G, M, V, W, LRa, B1, B2, EPS, step,
+                               vp(ws.data_ptr()), ws_bytes, stream)
+
+
+def _ref64(p, g, m, v, lr, step):
+    p, g, m, v = (t.double() for t in (p, g, m, v))
+    m = m + (g - m) * (1 - B1)
+    v = v * B2 + (1 - B2) * g * g
+    bc1, bc2 = 1 - B1 ** step, 1 - B2 ** step
+    return p - lr / bc1 * m / (v.sqrt() / bc2 ** 0.5 + EPS), m, v
+
+
+@pytest.mark.parametrize("N", [0, 1, 4097, 1_000_003])
+@pytest.mark.parametrize("kind", ["empty", "full", "0.5%", "50%"])
+def test_adam_step_rows_matches_dense_and_float64(gs, dev, N, kind):
+    L = gs._lib.load()
+    step = 7
+    ts = _tensors(N, WIDTHS, dev, seed=N + 3)
+    mask = _mask(N, kind, dev, seed=N)
+    orig = [[t.clone() for t in x] for x in ts]
+    dense = [[t.clone() for t in x] for x in ts]
+    assert _call(L, "rows", ts, N, mask, step, WIDTHS) == 0
+    if N:
+        assert _call(L, "dense", dense, N, mask, step, WIDTHS) == 0
+    torch.cuda.synchronize()
+    sel = mask.nonzero().reshape(-1)
+    off = (~mask).nonzero().reshape(-1)
+    for i, (got, was, den) in enumerate(zip(ts, orig, dense)):
+        assert torch.equal(got[1], was[1]), "gradient written"
+        for k in (0, 2, 3):
+            assert torch.equal(got[k][off], was[k][off]), (i, k, "masked-off row changed")
+            assert torch.equal(got[k][sel], den[k][sel]), (i, k, "selected row differs from gs_adam_step")
+        if kind == "full":
+            for k in (0, 2, 3):
+                assert torch.equal(got[k], den[k])
+        if sel.numel():
+            rp, rm, rv = _ref64(was[0][sel], was[1][sel], was[2][sel], was[3][sel], LR[i], step)
+            assert torch.allclose(got[0][sel].double(), rp, rtol=1e-5, atol=1e-6)
+            assert torch.allclose(got[2][sel].double(), rm, rtol=1e-5, atol=1e-7)
+            assert torch.allclose(got[3][sel].double(), rv, rtol=1e-5, atol=1e-10)
+
+
+def test_adam_step_rows_rejects_bad_arguments(gs, dev):
+    L = gs._lib.load()
+    ts = _tensors(16, [3] * 9, dev, seed=1)
+    mask = torch.ones(16, dtype=torch.bool, device=dev)
+    assert _call(L, "rows", ts, 16, mask, 1, [3] * 9) == 1            # more than 8 tensors in one launch
+    assert _call(L, "rows", ts[:2], 16, mask, 1, [3, 65]) == 1        # width above 64
+    assert _call(L, "rows", ts[:2], 16, mask, 0, [3, 3]) == 1         # step counts from 1
+    assert L.gs_adam_step_rows_workspace_bytes(0) == 0
+    assert L.gs_adam_step_rows_workspace_bytes(1_000_000) >= 4 * 1_000_000
+
+
+def test_adam_step_all_with_a_row_mask_and_more_than_8_tensors(gs, dev):
+    """ten per-row tensors (two launches of gs_adam_step_rows) and one parameter of another leading dimension (dense
+    gs_adam_step) through fused.adam_step_all: the masked rows step exactly as a dense HipAdam would step them"""
+    from gsdeblur_amd.fused import HipAdam, adam_step_all
+    N = 3001
+    g = torch.Generator(device=dev).manual_seed(5)
+    widths = [1, 3, 4, 45, 64, 3, 3, 1, 16, 2]
+    ps = [torch.nn.Parameter(torch.randn(N, w, device=dev, generator=g)) for w in widths]
+    cam = torch.nn.Parameter(torch.randn(7, 6, device=dev, generator=g))
+    ref_ps = [torch.nn.Parameter(p.detach().clone()) for p in ps]
+    ref_cam = torch.nn.Parameter(cam.detach().clone())
+    opts = [HipAdam([p], lr=1e-3 * (i + 1), eps=1e-15, selective=True) for i, p in enumerate(ps)]
+    opts.append(HipAdam([cam], lr=1e-2, eps=1e-15))
+    ref = [HipAdam([p], lr=1e-3 * (i + 1), eps=1e-15) for i, p in enumerate(ref_ps)] + \
+        [HipAdam([ref_cam], lr=1e-2, eps=1e-15)]
+    masks = [torch.rand(N, device=dev, generator=g) < d for d in (0.3, 0.05, 0.6)]
+    for step, mask in enumerate(masks):
+        for p, q in zip(ps + [cam], ref_ps + [ref_cam]):
+            p.grad = torch.randn(p.shape, device=dev, generator=g)
+            q.grad = p.grad.clone()
+        before = [(p.detach().clone(), o.state[p]["exp_avg"].clone() if o.state[p] else None)
+                  for p, o in zip(ps, opts[:-1])]
+        adam_step_all(opts, row_mask=mask)
+        # the reference: a dense step of copies whose unselected rows are then put back
+        for q, o in zip(ref_ps + [ref_cam], ref):
+            o.step()
+        for i, (p, q) in enumerate(zip(ps, ref_ps)):
+            st, rst = opts[i].state[p], ref[i].state[q]
+            assert st["step"] == step + 1
+            assert torch.equal(p.detach()[mask], q.detach()[mask]), i
+            assert torch.equal(st["exp_avg"][mask], rst["exp_avg"][mask]), i
+            assert torch.equal(p.detach()[~mask], before[i][0][~mask]), i
+            if before[i][1] is not None:
+                assert torch.equal(st["exp_avg"][~mask], before[i][1][~mask]), i
+            # keep the reference in lock step with the selective state
+            with torch.no_grad():
+                q.copy_(p)
+                rst["exp_avg"].copy_(st["exp_avg"])
+                rst["exp_avg_sq"].copy_(st["exp_avg_sq"])
+        assert torch.equal(cam.detach(), ref_cam.detach())          # the other leading dimension stepped densely
+
+
+def test_visible_rows_matches_radii_any(gs, dev):
+    from gsdeblur_amd.fused import visible_rows
+    g = torch.Generator(device=dev).manual_seed(2)
+    for shape in [(10, 4097), (3, 10, 1000), (1, 1), (50, 0)]:
+        r = torch.randint(-2, 3, shape, device=dev, generator=g, dtype=torch.int32)
+        r[r == 1] = 0
+        r2 = r.flatten(0, -2)
+        got = visible_rows(r2)
+        assert got.dtype == torch.bool and got.shape == (shape[-1],)
+        assert torch.equal(got, (r2 > 0).any(0)), shape
+
+
+# --------------------------------------------------------------------------- model-level
+def _model(gs, dev, mask_kind, W=128, H=96, n=3000, seed=21, num_cameras=8):
+    sc = _scene(gs, n, W, H, seed)
+    cfg = gs.SplatfactoDeblurConfig(sh_degree=3, blur_samples=3, gamma=2.2, min_rgb_level=0.0,
+                                    rolling_shutter_compensation=False, optimizer="selective_adam",
+                                    selective_mask=mask_kind)
+    model = gs.SplatfactoDeblurModel.from_scene(cfg, sc, dev, num_cameras=num_cameras)
+    return sc, model
+
+
+def _snapshot(model, opts):
+    snap = {}
+    for k, p in model.gauss_params().items():
+        st = opts[k].state.get(p, {})
+        snap[k] = (p.detach().clone(), {s: (v.clone() if torch.is_tensor(v) else v) for s, v in st.items()})
+    return snap
+
+
+def _check_selective_step(gs, model, opts, snap, mask):
+    """rows outside `mask` unchanged; rows inside equal a dense HipAdam step of the snapshot with the step's grads"""
+    from gsdeblur_amd.fused import HipAdam
+    N = model.num_points
+    assert mask.shape == (N,) and 0 < int(mask.sum()) < N, int(mask.sum())
+    for k, p in model.gauss_params().items():
+        p0, st0 = snap[k]
+        st = opts[k].state[p]
+        q = torch.nn.Parameter(p0.clone())
+        q.grad = p.grad.detach().clone()
+        ref = HipAdam([q], lr=opts[k].param_groups[0]["lr"], eps=1e-15)
+        if st0:
+            ref.state[q] = {"step": st0["step"], "exp_avg": st0["exp_avg"].clone(), "exp_avg_sq": st0["exp_avg_sq"].clone()}
+        ref.step()
+        rst = ref.state[q]
+        assert torch.equal(p.detach()[mask], q.detach()[mask]), k
+        assert torch.equal(st["exp_avg"][mask], rst["exp_avg"][mask]), k
+        assert torch.equal(st["exp_avg_sq"][mask], rst["exp_avg_sq"][mask]), k
+        assert torch.equal(p.detach()[~mask], p0[~mask]), k
+        if st0:
+            assert torch.equal(st["exp_avg"][~mask], st0["exp_avg"][~mask]), k
+            assert torch.equal(st["exp_avg_sq"][~mask], st0["exp_avg_sq"][~mask]), k
+        else:
+            assert not st["exp_avg"][~mask].any() and not st["exp_avg_sq"][~mask].any(), k
+
+
+def _expected_mask(model, kind):
+    N = model.num_points
+    if kind == "visible":
+        r = model.radii
+        r = torch.cat([x.reshape(-1, N) for x in r]) if isinstance(r, (list, tuple)) else r.reshape(-1, N)
+        return (r > 0).any(0)
+    return torch.stack([(p.grad.reshape(N, -1) != 0).any(1) for p in model.gauss_params().values()]).any(0)
+
+
+@pytest.mark.parametrize("kind", ["visible", "touched"])
+@pytest.mark.parametrize("batched", [False, True])
+def test_train_step_selective_adam(gs, dev, kind, batched):
+    W, H = 128, 96
+    sc, model = _model(gs, dev, kind, W, H)
+    cams = _views(gs, sc, W, H, 8)
+    # shift the views sideways so that a good share of the Gaussians falls outside each frustum
+    for c in cams:
+        c.camera_to_world = c.camera_to_world.clone()
+        c.camera_to_world[0, 3] += 0.6
+    opts = gs.training.make_optimizers(model)
+    assert all(getattr(opts[k], "selective", False) for k in model.gauss_params())
+    assert gs.training.one_call_route(model)
+    g = torch.Generator().manual_seed(4)
+    targets = [torch.rand(H, W, 3, generator=g).to(dev) for _ in cams]
+    for it in range(3):
+        if batched:
+            ids = [(2 * it) % 8, (2 * it + 3) % 8]
+            cam, tgt = [cams[i] for i in ids], [targets[i] for i in ids]
+        else:
+            cam, tgt = cams[it], targets[it]
+        snap = _snapshot(model, opts)
+        gs.training.train_step(model, opts, cam, tgt, 0.2)
+        if it == 0:
+            continue                          # the first step creates the state; the next ones are checked
+        _check_selective_step(gs, model, opts, snap, _expected_mask(model, kind))
+
+
+@pytest.mark.parametrize("kind", ["visible", "touched"])
+def test_selective_step_right_after_densification(gs, dev, kind):
+    """densification changes N (densify._swap_parameter carries the moments); the next step's mask has the new N"""
+    from gsdeblur_amd import densify as D
+    W, H = 128, 96
+    sc, model = _model(gs, dev, kind, W, H)
+    cams = _views(gs, sc, W, H, 4)
+    opts = gs.training.make_optimizers(model)
+    tgt = torch.rand(H, W, 3, generator=torch.Generator().manual_seed(9)).to(dev)
+    gs.training.train_step(model, opts, cams[0], tgt, 0.2)
+    N0 = model.num_points
+    keep = torch.ones(N0, dtype=torch.bool, device=dev)
+    keep[::7] = False                                          # cull every 7th row ...
+    dup = torch.arange(0, N0, 11, device=dev)                  # ... and duplicate every 11th
+    with torch.no_grad():
+        for name, p in list(model.gauss_params().items()):
+            D._swap_parameter(model, opts, name, torch.cat([p.detach()[keep], p.detach()[dup]]), keep, dup.numel())
+    N1 = model.num_points
+    assert N1 != N0
+    snap = _snapshot(model, opts)
+    gs.training.train_step(model, opts, cams[1], tgt, 0.2)
+    mask = _expected_mask(model, kind)
+    assert mask.shape == (N1,)
+    _check_selective_step(gs, model, opts, snap, mask)
+
+
+# Held-out PSNR of the short run below, measured on the MI355X: dense Adam 31.81 / 31.49 dB with shuffle seeds 0 / 1
+# (spread 0.32 dB), selective Adam 30.91 dB ("visible") and 31.12 dB ("touched") with seed 0.  A row that a view
+# missed keeps its momentum instead of coasting on it, so the selective runs follow another trajectory; the tolerance
+# against the mean of the two dense seeds is 3x the measured seed spread, rounded up to 1 dB.
+PSNR_TOL_DB = 1.0
+
+
+def test_selective_adam_trains_as_well_as_dense_adam(gs, dev, tmp_path):
+    import synthetic_dataset as SD
+    root = str(tmp_path / "ds")
+    info = SD.generate(root, dev, width=160, height=120, n_frames=17, n_gaussians=4000, speed=1.5, dense_samples=64)
+    scene = gs.load_transforms(root)
+    images = [gs.data.load_image(p, dev) for p in scene.image_paths]
+    gt = info["scene"]
+    g = torch.Generator().manual_seed(1)
+    start = dict(gt)
+    start["sh"] = gt["sh"] + 0.15 * torch.randn(gt["sh"].shape, generator=g) * (torch.arange(16) == 0)[None, :, None]
+    start["means"] = gt["means"] + 0.004 * torch.randn(gt["means"].shape, generator=g)
+    start["log_scales"] = gt["log_scales"] + 0.1
+    res = {}
+    for name, opt, kind, seed in (("adam_s0", "adam", "visible", 0), ("adam_s1", "adam", "visible", 1),
+                                  ("visible", "selective_adam", "visible", 0),
+                                  ("touched", "selective_adam", "touched", 0)):
+        cfg = gs.SplatfactoDeblurConfig(sh_degree=3, blur_samples=5, gamma=2.2, min_rgb_level=0.0,
+                                        rolling_shutter_compensation=False, optimizer=opt, selective_mask=kind)
+        model = gs.SplatfactoDeblurModel.from_scene(cfg, start, dev, num_cameras=len(scene.cameras))
+        res[name] = gs.training.train_scene(model, scene, images, iterations=400, seed=seed)["results"]["psnr"]
+    print("held-out PSNR:", {k: round(v, 3) for k, v in res.items()})
+    dense = 0.5 * (res["adam_s0"] + res["adam_s1"])
+    print("seed spread", round(abs(res["adam_s0"] - res["adam_s1"]), 3), "tolerance", PSNR_TOL_DB)
+    for name in ("visible", "touched"):
+        assert res[name] > dense - PSNR_TOL_DB, res

@@ -40,6 +40,10 @@ def main():
     ap.add_argument("--iterations", type=int, default=1500)
     ap.add_argument("--optimize-eval-cameras", action="store_true")
     ap.add_argument("--pose-noise", type=float, default=0.0, help="std (m / rad) of noise on the evaluation poses")
+    ap.add_argument("--optimizer", default="adam", choices=["adam", "selective_adam"],
+                    help="selective_adam: the Gaussian rows step only when a training view reached them")
+    ap.add_argument("--selective-mask", default="visible", choices=["visible", "touched"],
+                    help="selective_adam's rows: radii > 0 in the step's view (visible) or a non-zero gradient (touched)")
     ap.add_argument("--out", default="gpurun_out/deblur")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
@@ -64,7 +68,8 @@ def main():
                                                                       args.rolling_shutter_mode != "off"),
                                         rolling_shutter_mode="exact" if args.rolling_shutter_mode == "exact" else "bands",
                                         rs_bands=min(8, (scene.cameras[0].height + 15) // 16),
-                                        motion_model=args.motion_model, use_scale_regularization=True)
+                                        motion_model=args.motion_model, use_scale_regularization=True,
+                                        optimizer=args.optimizer, selective_mask=args.selective_mask)
         if args.optimize_eval_cameras:
             cfg.camera_optimizer.mode = "SO3xR3"
         model = SD.init_from_seed_points(cfg, xyz, rgb, dev, num_cameras=len(scene.cameras))
