@@ -87,6 +87,7 @@ _SIGS = {
     "gs_frame_forward": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P, _L, _P, _P],
     "gs_frame_backward": [_P, _P, _P, _P, _P, _P, _P, _P, _F, _F, _I, _P, _P, _P, _P, _P, _L, _P],
     "gs_frame_backward_depth": [_P, _P, _P, _P, _P, _P, _P, _P, _F, _F, _I, _P, _P, _P, _P, _P, _L, _P, _P],
+    "gs_xy_absgrad_sum": [_I, _I, _I, _P, _P, _P, _P],
     "gs_frame_profile_enable": [ctypes.c_uint],
     "gs_frame_profile_read": [_I, _P, _P],
     "gs_image_loss_fwd_bwd": [_I, _I, _P, _P, _F, _P, _P, _P, _L, _P],

@@ -753,6 +753,9 @@ GS_EXPORT int gs_frame_forward(const gs_frame_desc* dp, float* records, unsigned
 // depth (the forward's out_depth): non-NULL runs the depth specialisations of the compositors and of the tuple reduce,
 // which leave d loss / d depth in v_records[.., 11] (the projection backward reads it with grad flag 64).  NULL: the
 // launches of gs_frame_backward, byte for byte.
+// bwd_variant bit GS_BWD_ABSGRAD (2048; SE(3) frames only — the pixel-velocity compositor keeps d loss / d pixel velocity
+// in the same tuple slots and refuses it): the absgrad specialisations of the compositors, with or without v_depth; the
+// reduce then leaves the per-pair absolute centre gradients in v_records[.., 9..10] (gs_xy_absgrad_sum reads them).
 GS_EXPORT int gs_frame_backward_depth(const gs_frame_state* state, const float* records, const float* background,
                                       const int* band_edges, const float* out_T, const float* v_img, const float* v_alpha,
                                       const float* cmb_scale, float cmb_gamma, float cmb_min_level, int bwd_variant,
@@ -778,6 +781,7 @@ GS_EXPORT int gs_frame_backward_depth(const gs_frame_state* state, const float* 
   // ONE tuple buffer for all slices: a slice's tuples are reduced before the next (nearer) slice writes its own
   const bool shared = state->shared_list != 0;
   if (shared && (!pix_vel || !sample_times)) return GS_ERR_INVALID;
+  if ((bwd_variant & GS_BWD_ABSGRAD) && (state->rolling_shutter_time != 0.f || shared)) return GS_ERR_INVALID;
   const long long tpe = shared ? S : 1;                               // gradient tuples per list entry
   float* tuples = A.take<float>(12 * maxI * tpe);
   unsigned char* flags = A.take<unsigned char>((maxI * tpe + 15) & ~15ll);      // (whole 16-byte words: see the fill below)

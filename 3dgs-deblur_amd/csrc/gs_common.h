@@ -9,6 +9,10 @@
 #define GS_ERR_WORKSPACE 3
 // launch errors are returned as 1000 + hipError_t
 
+// bwd_variant bit of gs_frame_backward / gs_rasterize_bwd_slice: the absgrad specialisations of the backward compositor
+// (include/gsdeblur.h)
+#define GS_BWD_ABSGRAD 2048
+
 #define GS_EXPORT extern "C" __attribute__((visibility("default")))
 
 static inline int gs_launch_status() {

@@ -1379,6 +1379,35 @@ __global__ __launch_bounds__(256) void xy_grad_cams_kernel(int N, int P, int B, 
   }
 }
 
+// Absgrad (the densification statistic of AbsGS): camera b's sum over ITS sub-poses, in sub-pose order, of slots 9
+// and 10 of the gradient records — the per-(pixel, Gaussian) absolute centre gradients the absgrad instantiations of the
+// backward compositor reduce (raster_bwd.hip) — touched rows only.  One thread per Gaussian, all B rows written.
+__global__ __launch_bounds__(256) void xy_absgrad_cams_kernel(int N, int P, int B, const float* __restrict__ v_records,
+                                                              const unsigned char* __restrict__ touched,
+                                                              float* __restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N) return;
+  const int Pc = P / B;
+  for (int b = 0; b < B; ++b) {
+    float ax = 0.f, ay = 0.f;
+    for (int p = b * Pc; p < (b + 1) * Pc; ++p) {
+      const size_t idx = (size_t)p * N + i;
+      if (!touched[idx]) continue;
+      const float* g = v_records + idx * kGradFloats;
+      ax += g[9]; ay += g[10];
+    }
+    *reinterpret_cast<float2*>(out + ((size_t)b * N + i) * 2) = make_float2(ax, ay);
+  }
+}
+
+GS_EXPORT int gs_xy_absgrad_sum(int N, int P, int cameras, const float* v_records, const unsigned char* touched,
+                                float* out, void* stream) {
+  if (N <= 0 || P <= 0 || cameras < 1 || P % cameras != 0 || !v_records || !touched || !out) return GS_ERR_INVALID;
+  hipLaunchKernelGGL(xy_absgrad_cams_kernel, dim3((N + 255) / 256), dim3(256), 0, (hipStream_t)stream, N, P, cameras,
+                     v_records, touched, out);
+  return gs_launch_status();
+}
+
 // Scratch of the deterministic pose-gradient reduction (gs_project_bwd: P = 1, with_touched = 0; gs_project_fused_bwd /
 // gs_project_pixvel_bwd: with_touched = whether touched flags are passed).  Needed only when a view-matrix / twist
 // gradient is asked for.

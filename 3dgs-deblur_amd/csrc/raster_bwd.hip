@@ -299,8 +299,11 @@ constexpr int kRedCols4 = 32, kRedStride4 = 36;    // 36 = 32 + 4: rows 16-byte 
 #endif
 constexpr int kRedFloats4 = kRedG4 * 9 * kRedStride4;
 // the depth-gradient specialisation reduces a tenth row per entry: sum of weight * v_depth (tuple slot 11)
-constexpr int red_rows(bool depth) { return depth ? 10 : 9; }
-constexpr int red_floats(bool depth) { return kRedG4 * red_rows(depth) * kRedStride4; }
+// the absgrad specialisations reduce two more rows per entry, BEFORE the depth row: the sums over the entry's pixels of
+// |d loss / d x| and |d loss / d y| of each (pixel, Gaussian) pair (tuple slots 9 and 10), so that with both switches
+// the depth row is row 11 = its tuple slot
+constexpr int red_rows(bool depth, bool absgrad = false) { return 9 + (absgrad ? 2 : 0) + (depth ? 1 : 0); }
+constexpr int red_floats(bool depth, bool absgrad = false) { return kRedG4 * red_rows(depth, absgrad) * kRedStride4; }
 
 // w[i] = v[i](lane) + v[i](lane ^ 1) for nine values: nine v_add_f32_dpp in one block (the DPP combiner leaves most
 // of them as v_mov_b32_dpp + v_add_f32 otherwise).  The s_nop covers the VALU-write -> DPP-read hazard, which the
@@ -328,6 +331,15 @@ __device__ __forceinline__ void pair_sum1(float& v) {
       : "+v"(v));
 }
 
+// w = v(lane) + v(lane ^ 1) for two values (the absgrad rows; s_nop as in pair_sum9)
+__device__ __forceinline__ void pair_sum2(float& a, float& b) {
+  asm volatile(
+      "s_nop 1\n\t"
+      "v_add_f32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+      "v_add_f32_dpp %1, %1, %1 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf"
+      : "+v"(a), "+v"(b));
+}
+
 // ---------------------------------------------------------------------------
 // One list entry against the lane's four pixels (returns whether any lane of the wave was hit; then the lane's 9
 // partial sums are in LDS rows slot*9 .. slot*9+8, column `lane >> 1`).
@@ -350,9 +362,14 @@ __device__ __forceinline__ void pair_sum1(float& v) {
 // DEPTH (a depth gradient is present): the camera-space depth is a fourth colour channel with background 0 — the pixel's
 // v_depth joins the colour dot product cv (so v_alpha and the behind-sum Dv carry it: no extra per-pixel state between
 // slices) and the entry's tenth partial sum, sum of weight * v_depth, is d loss / d depth (tuple slot 11).
+// ABSGRAD (the caller asked for xy_absgrad_out): the moments give the SIGNED sum of the centre gradient only, so the
+// absolute values are taken per pixel, per component, before any summation: ax += |v_sigma * (cx dx + cy dy)|,
+// ay += |v_sigma * (cy dx + cz dy)| (a pixel that is not hit has v_sigma = 0 and adds an exact zero).  |.| is a source
+// modifier: the loop grows by four VALU per pixel (two fma for the bracket, two fma with |.| operands for the sums) and
+// four multiplies per entry (cx dx, cy dx for both column halves).  Rows 9 and 10 = tuple slots 9 and 10.
 struct BwdQuad { float T[4], Dv[4], vr[4], vg[4], vb[4], py[4], vd[4]; int fin[4]; };
 
-template <bool CLAMP, bool RAW_OP, bool DEPTH>
+template <bool CLAMP, bool RAW_OP, bool DEPTH, bool ABSGRAD = false>
 __device__ __forceinline__ bool bwd_entry(const RecS& rc, float pxf, int idx, BwdQuad& pp, float* __restrict__ red,
                                           int slot, int lane, float agm) {
   // pxf: the lane's pixel-centre column in the LEFT quadrants; the right ones are 8 further (exact in fp32)
@@ -361,6 +378,8 @@ __device__ __forceinline__ bool bwd_entry(const RecS& rc, float pxf, int idx, Bw
   const float hx[2] = {fmaf(rc.qx * dxa, dxa, rc.nmid), fmaf(rc.qx * dxb, dxb, rc.nmid)};
   const float bx[2] = {qyn * dxa, qyn * dxb};
   float m0[2] = {0.f, 0.f}, m1[2] = {0.f, 0.f}, m2 = 0.f, q_r = 0.f, q_g = 0.f, q_b = 0.f, q_d = 0.f;
+  float ax = 0.f, ay = 0.f;
+  const float cxdx[2] = {rc.cx * dxa, rc.cx * dxb}, cydx[2] = {rc.cy * dxa, rc.cy * dxb};      // ABSGRAD only
   bool any = false;
   // (measured negatives, removed in round 6 — the records are in profiles/: the six per-entry record fields copied to
   //  VGPRs once per entry instead of 24 SGPR-operand uses; lanes that did not blend the entry sitting the body out under
@@ -389,6 +408,10 @@ __device__ __forceinline__ bool bwd_entry(const RecS& rc, float pxf, int idx, Bw
     m0[k & 1] += v_sigma;
     m1[k & 1] += vsdy;
     m2 = fmaf(vsdy, dy, m2);
+    if (ABSGRAD) {
+      ax = fmaf(fabsf(v_sigma), fabsf(fmaf(rc.cy, dy, cxdx[k & 1])), ax);
+      ay = fmaf(fabsf(v_sigma), fabsf(fmaf(rc.cz, dy, cydx[k & 1])), ay);
+    }
   }
   if (!any) return false;
   // sum over the lane's pixels of v_sigma * {1, dx, dx^2} and of v_sigma * dy * {1, dx}
@@ -402,27 +425,30 @@ __device__ __forceinline__ bool bwd_entry(const RecS& rc, float pxf, int idx, Bw
   const float p_op = RAW_OP ? M0 : -M0 * __builtin_amdgcn_rcpf(rc.op);
   float w[9] = {p_x, p_y, p_cx, p_cy, p_cz, p_op, q_r, q_g, q_b};
   pair_sum9(w);
+  if (ABSGRAD) pair_sum2(ax, ay);
   if (DEPTH) pair_sum1(q_d);
   if ((lane & 1) == 0) {
-    float* r0 = red + slot * (red_rows(DEPTH) * kRedStride4) + (lane >> 1);
+    float* r0 = red + slot * (red_rows(DEPTH, ABSGRAD) * kRedStride4) + (lane >> 1);
 #pragma unroll
     for (int c = 0; c < 9; ++c) r0[c * kRedStride4] = w[c];
-    if (DEPTH) r0[9 * kRedStride4] = q_d;
+    if (ABSGRAD) { r0[9 * kRedStride4] = ax; r0[10 * kRedStride4] = ay; }
+    if (DEPTH) r0[(ABSGRAD ? 11 : 9) * kRedStride4] = q_d;
   }
   return true;
 }
 
 // the tile's list, back to front, entries [range_x, wave_end)
-template <bool CLAMP, int OUT, bool DEPTH, class State>
+template <bool CLAMP, int OUT, bool DEPTH, bool ABSGRAD = false, class State>
 __device__ __forceinline__ void bwd_walk(const int* __restrict__ ids, const int* __restrict__ eids,
                                          const float* __restrict__ records, unsigned max_id, int range_x, int wave_end,
                                          unsigned n, float pxf, float agm, State& pp, float* __restrict__ red,
                                          int lane, float* __restrict__ v_records, float* __restrict__ tuples,
                                          unsigned char* __restrict__ flags) {
-  constexpr int kRows = red_rows(DEPTH);
-  const int row = lane;                                    // row-sum role: lanes 0..35 (0..39 with DEPTH)
+  constexpr int kRows = red_rows(DEPTH, ABSGRAD);
+  const int row = lane;                                    // row-sum role: lanes 0..35 (0..39 with DEPTH; ABSGRAD: 0..43 / 0..47)
   const int row_g = row / kRows, row_c = row - row_g * kRows;
-  const int slot_c = (DEPTH && row_c == 9) ? 11 : row_c;   // tuple / gradient-record slot of the row (depth: 11)
+  // tuple / gradient-record slot of the row (depth: 11; with ABSGRAD every row is its own slot, the depth row is row 11)
+  const int slot_c = (DEPTH && !ABSGRAD && row_c == 9) ? 11 : row_c;
   const int4* __restrict__ ids4 = reinterpret_cast<const int4*>(ids);
   const int4* __restrict__ eids4 = reinterpret_cast<const int4*>(eids);
   int b = (wave_end - 1) & ~3;
@@ -441,14 +467,14 @@ __device__ __forceinline__ void bwd_walk(const int* __restrict__ ids, const int*
     idv = ids4[max(b - 4, 0) >> 2];
     asm volatile("" ::: "memory");
     unsigned filled = 0;
-    if ((unsigned)(b + 3 - range_x) < n && bwd_entry<CLAMP, OUT == 1, DEPTH>(a0, pxf, b + 3, pp, red, 3, lane, agm)) filled |= 8u;
-    if ((unsigned)(b + 2 - range_x) < n && bwd_entry<CLAMP, OUT == 1, DEPTH>(a1, pxf, b + 2, pp, red, 2, lane, agm)) filled |= 4u;
+    if ((unsigned)(b + 3 - range_x) < n && bwd_entry<CLAMP, OUT == 1, DEPTH, ABSGRAD>(a0, pxf, b + 3, pp, red, 3, lane, agm)) filled |= 8u;
+    if ((unsigned)(b + 2 - range_x) < n && bwd_entry<CLAMP, OUT == 1, DEPTH, ABSGRAD>(a1, pxf, b + 2, pp, red, 2, lane, agm)) filled |= 4u;
     // pair B is ready; refill pair A from the next group
     asm volatile("" :: "s"(b0.x), "s"(b1.x), "s"(idv.x), "s"(ev.x) : "memory");
     a0 = load_rec_s<DEPTH>(records, min((unsigned)idv.w, max_id)); a1 = load_rec_s<DEPTH>(records, min((unsigned)idv.z, max_id));
     asm volatile("" ::: "memory");
-    if ((unsigned)(b + 1 - range_x) < n && bwd_entry<CLAMP, OUT == 1, DEPTH>(b0, pxf, b + 1, pp, red, 1, lane, agm)) filled |= 2u;
-    if ((unsigned)(b - range_x) < n && bwd_entry<CLAMP, OUT == 1, DEPTH>(b1, pxf, b, pp, red, 0, lane, agm)) filled |= 1u;
+    if ((unsigned)(b + 1 - range_x) < n && bwd_entry<CLAMP, OUT == 1, DEPTH, ABSGRAD>(b0, pxf, b + 1, pp, red, 1, lane, agm)) filled |= 2u;
+    if ((unsigned)(b - range_x) < n && bwd_entry<CLAMP, OUT == 1, DEPTH, ABSGRAD>(b1, pxf, b, pp, red, 0, lane, agm)) filled |= 1u;
     if (filled) {
       __builtin_amdgcn_wave_barrier();
       if (row < kRedG4 * kRows && ((filled >> row_g) & 1u)) {
@@ -487,7 +513,7 @@ __device__ __forceinline__ void pix_get(const BwdQuad& st, int k, float& T, floa
 // their names, which profiles/traffic.json's ISA hashes and tests/test_occupancy.py key on) exactly as they were.
 #define GS_BWD_NO_DEPTH_PARAM
 #define GS_BWD_DEPTH_PARAM , const float* __restrict__ v_depth
-#define GS_BWD_SLOAD_KERNEL(NAME, DEPTH, DEPTH_PARAM, PROLOGUE, CMB_ROW)                                                        \
+#define GS_BWD_SLOAD_KERNEL(NAME, DEPTH, ABSGRAD, DEPTH_PARAM, PROLOGUE, CMB_ROW)                                                        \
 template <bool STATE, int OUT>                                                                                          \
 __global__ __launch_bounds__(256, GS_BWD_SLOAD_WAVES) void NAME(                                                        \
     RasterParams prm, const int* __restrict__ ids /*record index per sorted entry, padded*/,                            \
@@ -498,9 +524,9 @@ __global__ __launch_bounds__(256, GS_BWD_SLOAD_WAVES) void NAME(                
     float* __restrict__ tuples, unsigned char* __restrict__ flags,                                                      \
     const unsigned char* __restrict__ tile_hot DEPTH_PARAM) {                                                           \
   PROLOGUE                                                                                                              \
-  __shared__ __attribute__((aligned(16))) float lds_all[4 * red_floats(DEPTH)];                                        \
+  __shared__ __attribute__((aligned(16))) float lds_all[4 * red_floats(DEPTH, ABSGRAD)];                              \
   const int lane = lane_id();                                                                                                                 \
-  float* red = lds_all + (threadIdx.x >> 6) * red_floats(DEPTH);   /* wave-private */                                                         \
+  float* red = lds_all + (threadIdx.x >> 6) * red_floats(DEPTH, ABSGRAD);   /* wave-private */                                                \
   const int T = prm.tiles_x * prm.tiles_y;                                                                                                    \
   const unsigned work = (unsigned)__builtin_amdgcn_readfirstlane(                                                                             \
       (int)(xcd_remap(blockIdx.x, n_blocks) * 4u + (threadIdx.x >> 6)));                                                                      \
@@ -556,8 +582,8 @@ _Pragma("unroll")                                                               
   const float agm = prm.alpha_grad_max;                                                                                                       \
   if (n != 0u) {                                                                                                                              \
     const bool hot = tile_hot == nullptr || __builtin_amdgcn_readfirstlane((int)tile_hot[(size_t)p * T + t]) != 0;                            \
-    if (hot) bwd_walk<true, OUT, DEPTH>(ids, eids, records, max_id, range.x, wave_end, n, pxf, agm, pp, red, lane, v_records, tuples, flags); \
-    else bwd_walk<false, OUT, DEPTH>(ids, eids, records, max_id, range.x, wave_end, n, pxf, agm, pp, red, lane, v_records, tuples, flags);    \
+    if (hot) bwd_walk<true, OUT, DEPTH, ABSGRAD>(ids, eids, records, max_id, range.x, wave_end, n, pxf, agm, pp, red, lane, v_records, tuples, flags); \
+    else bwd_walk<false, OUT, DEPTH, ABSGRAD>(ids, eids, records, max_id, range.x, wave_end, n, pxf, agm, pp, red, lane, v_records, tuples, flags); \
   }                                                                                                                                           \
   if (STATE) {                                                                                                                                \
 _Pragma("unroll")                                                                                                                                \
@@ -577,17 +603,27 @@ _Pragma("unroll")                                                               
   }                                                                                                                                           \
 }
 
-GS_BWD_SLOAD_KERNEL(raster_bwd_sload_kernel, false, GS_BWD_NO_DEPTH_PARAM, const float* const v_depth = nullptr; (void)v_depth;,
+GS_BWD_SLOAD_KERNEL(raster_bwd_sload_kernel, false, false, GS_BWD_NO_DEPTH_PARAM, const float* const v_depth = nullptr; (void)v_depth;,
                     (size_t)y)
-GS_BWD_SLOAD_KERNEL(raster_bwd_depth_kernel, true, GS_BWD_DEPTH_PARAM, , (size_t)y)
+GS_BWD_SLOAD_KERNEL(raster_bwd_depth_kernel, true, false, GS_BWD_DEPTH_PARAM, , (size_t)y)
 // frames of several cameras (gs_frame_desc.cameras > 1): sample image s belongs to camera s / s_cam, whose combine scale
 // is row block s / s_cam of cmb_scale [B,H,W,3].  Separately named instantiations (launched only for B > 1), so the two
 // default kernels above keep their names and instruction streams.
 #define GS_BWD_CAMS_PARAM , int s_cam
 #define GS_BWD_DEPTH_CAMS_PARAM , const float* __restrict__ v_depth, int s_cam
-GS_BWD_SLOAD_KERNEL(raster_bwd_sload_cams_kernel, false, GS_BWD_CAMS_PARAM,
+GS_BWD_SLOAD_KERNEL(raster_bwd_sload_cams_kernel, false, false, GS_BWD_CAMS_PARAM,
                     const float* const v_depth = nullptr; (void)v_depth;, (size_t)(s / s_cam) * prm.H + y)
-GS_BWD_SLOAD_KERNEL(raster_bwd_depth_cams_kernel, true, GS_BWD_DEPTH_CAMS_PARAM, , (size_t)(s / s_cam) * prm.H + y)
+GS_BWD_SLOAD_KERNEL(raster_bwd_depth_cams_kernel, true, false, GS_BWD_DEPTH_CAMS_PARAM, , (size_t)(s / s_cam) * prm.H + y)
+// absgrad (variant bit GS_BWD_ABSGRAD: the caller asked for xy_absgrad_out): two more reduced rows per entry, the sums of
+// |d loss / d x| and |d loss / d y| per (pixel, Gaussian) pair, in tuple slots 9 and 10 of EVERY flagged tuple.  Four
+// separately named instantiations — {rgb, rgb + depth} x {one camera, several} — launched only with that bit, tuple form.
+GS_BWD_SLOAD_KERNEL(raster_bwd_absgrad_kernel, false, true, GS_BWD_NO_DEPTH_PARAM,
+                    const float* const v_depth = nullptr; (void)v_depth;, (size_t)y)
+GS_BWD_SLOAD_KERNEL(raster_bwd_absgrad_depth_kernel, true, true, GS_BWD_DEPTH_PARAM, , (size_t)y)
+GS_BWD_SLOAD_KERNEL(raster_bwd_absgrad_cams_kernel, false, true, GS_BWD_CAMS_PARAM,
+                    const float* const v_depth = nullptr; (void)v_depth;, (size_t)(s / s_cam) * prm.H + y)
+GS_BWD_SLOAD_KERNEL(raster_bwd_absgrad_depth_cams_kernel, true, true, GS_BWD_DEPTH_CAMS_PARAM, ,
+                    (size_t)(s / s_cam) * prm.H + y)
 
 // ---------------------------------------------------------------------------
 // Splat-parallel backward (round 6; VERDICT round 5 item 2a: "build, not cost").  MEASURED NEGATIVE, kept selectable
@@ -760,7 +796,8 @@ __device__ __forceinline__ void reduce_tuples_body(int n_slice, const unsigned* 
   // mult: tuples per list entry (gs_rasterize_bwd_rs_slice with one list for S samples writes S of them, adjacent)
   if (j < n_slice) { cnt = counts[j] * mult; e0 = cum[j] * mult; gi = slice_gi[j]; }
   // 11 components: slots 9 and 10 carry d loss / d pixel-velocity of the exact rolling-shutter compositor
-  // (raster_rs.hip); the other compositors leave them unwritten and nobody reads their sums
+  // (raster_rs.hip), or the absgrad sums of the SE(3) compositors' absgrad instantiations (every flagged tuple of such a
+  // launch has both written); the other compositors leave them unwritten and nobody reads their sums
   constexpr int kComp = tuple_comp(DEPTH);
   float acc[kComp];
 #pragma unroll
@@ -938,6 +975,8 @@ GS_EXPORT int gs_rasterize_bwd(const float* records, const int* sorted_vals, con
 // cameras > 1 (a frame of several cameras, S = cameras * samples per camera) with cmb_scale [cameras,H,W,3]: the
 // camera-indexed instantiations, tuple form and variant 0 only (anything else is refused).  Without cmb_scale (v_img
 // holds the per-sample gradients) the camera count changes nothing.
+// variant bit GS_BWD_ABSGRAD: the absgrad instantiations (tuple form, default variant only: with any of 1, 2 or 1024
+// the call is refused), which also write tuple slots 9 and 10 of every flagged tuple.
 extern "C" int gs_rasterize_bwd_slice_depth(const float* records, const int* sorted_vals, const int* tile_bins,
                                             const int* band_edges, const float* background, int S, int R, int H, int W,
                                             const float* out_T, const int* final_idx, const float* v_img,
@@ -959,6 +998,33 @@ extern "C" int gs_rasterize_bwd_slice_depth(const float* records, const int* sor
   // scalar-cache kernels: record index per sorted entry = sorted_ids, or sorted_vals itself when it holds Gaussian ids
   const int* ids = sorted_ids ? sorted_ids : (gi_of_e ? nullptr : sorted_vals);
   const unsigned max_id = (unsigned)(n_records > 0 ? n_records - 1 : 0);
+  if (variant & GS_BWD_ABSGRAD) {
+    // absgrad: its own instantiations, {rgb, rgb + depth} x {one camera's combine scale, one per camera}
+    if (variant != GS_BWD_ABSGRAD || n_records <= 0 || !ids || !tup) return GS_ERR_INVALID;
+    const bool cams = cameras > 1 && cmb_scale;
+    if (cams && S % cameras != 0) return GS_ERR_INVALID;
+    const int s_cam = cams ? S / cameras : S;
+    float* const bT = (bwd_T && bwd_B) ? bwd_T : nullptr;
+    float* const bB = bT ? bwd_B : nullptr;
+#define GS_LAUNCH_ABSGRAD(KERNEL, STATE, ...)                                                                           \
+    hipLaunchKernelGGL((KERNEL<STATE, 1>), dim3(blocks), dim3(256), 0, st, prm, ids, sorted_vals, records, max_id, out_T, \
+                       final_idx, v_img, v_alpha, v_records, blocks, bT, bB, tuples, flags, tile_hot, ##__VA_ARGS__)
+    if (cams && v_depth) {
+      if (bT) GS_LAUNCH_ABSGRAD(raster_bwd_absgrad_depth_cams_kernel, true, v_depth, s_cam);
+      else GS_LAUNCH_ABSGRAD(raster_bwd_absgrad_depth_cams_kernel, false, v_depth, s_cam);
+    } else if (cams) {
+      if (bT) GS_LAUNCH_ABSGRAD(raster_bwd_absgrad_cams_kernel, true, s_cam);
+      else GS_LAUNCH_ABSGRAD(raster_bwd_absgrad_cams_kernel, false, s_cam);
+    } else if (v_depth) {
+      if (bT) GS_LAUNCH_ABSGRAD(raster_bwd_absgrad_depth_kernel, true, v_depth);
+      else GS_LAUNCH_ABSGRAD(raster_bwd_absgrad_depth_kernel, false, v_depth);
+    } else {
+      if (bT) GS_LAUNCH_ABSGRAD(raster_bwd_absgrad_kernel, true);
+      else GS_LAUNCH_ABSGRAD(raster_bwd_absgrad_kernel, false);
+    }
+#undef GS_LAUNCH_ABSGRAD
+    return gs_launch_status();
+  }
   if (cameras > 1 && cmb_scale) {
     // several cameras, fused combine: the camera-indexed instantiations (tuple form, the default variant only; the
     // splat-parallel measurement form and the round-1 kernels read one camera's scale and refuse a batch)

@@ -17,6 +17,14 @@ With motion-blur sub-poses the screen-space gradient of a Gaussian is the SUM ov
 per-sub-pose centre gradients (``render_subposes(..., xy_grad_out=)`` — written by the HIP projection
 backward, no extra pass) and its radius the largest over the sub-poses.
 
+That sum is SIGNED: pixels that push a Gaussian left and pixels that push it right cancel, and so do the sub-poses of a
+blurred frame — the Gaussian that is too large for the detail under it reports "nothing to do".  ``DensifyConfig.absgrad``
+accumulates the norm of the absgrad statistic instead (``render_subposes(..., xy_absgrad_out=)``: the absolute value of
+every (pixel, Gaussian) pair's contribution, per component, summed over pixels and sub-poses; AbsGS, gsplat's
+``absgrad``).  Absgrad is never smaller than the signed norm, so the same ``densify_grad_thresh`` densifies more;
+upstream recommends a higher threshold with it (recollected: 0.0008 instead of 0.0002 in gsplat's units).  The default
+threshold is not changed here: the choice belongs to the caller.
+
 Everything here is torch tensor surgery on whatever device the model lives on — no kernel of its own.
 Data parallel (dp.py): the statistics are summed / max-ed over the ranks before the decision and the split
 noise comes from a generator seeded by the step, so every rank takes the identical decision and the
@@ -51,36 +59,52 @@ class DensifyConfig:
     stop_split_at: int = 15000
     num_train_data: int = 0                 # training images per pass (upstream's post-reset guard)
     seed: int = 0
+    # accumulate the norm of the absgrad statistic (model.xy_absgrad) instead of the signed sum (model.xy_grad); needs
+    # SplatfactoDeblurConfig.densify_absgrad.  densify_grad_thresh keeps its value: see the module docstring
+    absgrad: bool = False
 
 
 class DensifyState:
     """Per-Gaussian accumulators between two refinements."""
 
-    def __init__(self, num_points: int, device):
+    def __init__(self, num_points: int, device, absgrad: bool = False):
+        self.absgrad = bool(absgrad)        # DensifyConfig.absgrad: which statistic xys_grad_norm accumulates
         self.xys_grad_norm = torch.zeros(num_points, device=device)
         self.vis_counts = torch.zeros(num_points, device=device)
         self.max_2Dsize = torch.zeros(num_points, device=device)
         self.size = (1, 1)
 
     @torch.no_grad()
-    def after_backward(self, radii: Tensor, xy_grad: Tensor, width: int, height: int) -> None:
+    def after_backward(self, radii: Tensor, xy_grad: Optional[Tensor], width: int, height: int,
+                       xy_absgrad: Optional[Tensor] = None) -> None:
         """radii int32 [P,N] (0 = culled in that sub-pose), xy_grad float32 [N,2] in pixels.  A batch of B cameras
         (render_batch): xy_grad [B,N,2] and radii [B,P,N] — each camera counts as one observation, exactly as B calls
-        with one camera each."""
-        if isinstance(xy_grad, (list, tuple)):
+        with one camera each.
+        xy_absgrad (same shapes as xy_grad): with ``absgrad`` set, xys_grad_norm accumulates its norm INSTEAD of
+        xy_grad's (which may then be None); without a tensor that is an error, never a fallback to the signed sum.
+        Everything else — visibility count, screen size — is the same for both statistics."""
+        stat = xy_grad
+        if self.absgrad:
+            if xy_absgrad is None:
+                raise ValueError("DensifyState(absgrad=True) needs xy_absgrad (render with xy_absgrad_out= / "
+                                 "SplatfactoDeblurConfig.densify_absgrad)")
+            stat = xy_absgrad
+        if isinstance(stat, (list, tuple)):
             # cameras rendered in several frames (model.get_outputs_batch with mixed intrinsics): per-camera tensors
-            for r, g in zip(radii, xy_grad):
-                self.after_backward(r, g, width, height)
+            for i, r in enumerate(radii):
+                self.after_backward(r, None if xy_grad is None else xy_grad[i], width, height,
+                                    None if xy_absgrad is None else xy_absgrad[i])
             return
-        if xy_grad.dim() == 3:
-            if radii.dim() != 3 or radii.shape[0] != xy_grad.shape[0]:
+        if stat.dim() == 3:
+            if radii.dim() != 3 or radii.shape[0] != stat.shape[0]:
                 raise ValueError("a batch's xy_grad [B,N,2] needs radii [B,P,N]")
-            for b in range(xy_grad.shape[0]):
-                self.after_backward(radii[b], xy_grad[b], width, height)
+            for b in range(stat.shape[0]):
+                self.after_backward(radii[b], None if xy_grad is None else xy_grad[b], width, height,
+                                    None if xy_absgrad is None else xy_absgrad[b])
             return
         radii = radii.reshape(-1, radii.shape[-1])
         visible = (radii > 0).any(dim=0)
-        self.xys_grad_norm += torch.where(visible, xy_grad.norm(dim=-1), torch.zeros_like(self.xys_grad_norm))
+        self.xys_grad_norm += torch.where(visible, stat.norm(dim=-1), torch.zeros_like(self.xys_grad_norm))
         self.vis_counts += visible.to(self.vis_counts.dtype)
         rel = radii.max(dim=0).values.to(torch.float32) / float(max(width, height))
         self.max_2Dsize = torch.where(visible, torch.maximum(self.max_2Dsize, rel), self.max_2Dsize)
@@ -226,7 +250,7 @@ def refine(model: SplatfactoDeblurModel, optimizers: Dict[str, torch.optim.Optim
                 new_value = torch.cat([new_value, extra[name][keep_new]])
             _swap_parameter(model, optimizers, name, new_value, keep_old, n_kept_new)
     n_after = model.num_points
-    fresh = DensifyState(n_after, dev)
+    fresh = DensifyState(n_after, dev, state.absgrad)
     fresh.size = state.size
     state.__dict__.update(fresh.__dict__)
     return {"split": n_split, "duplicated": n_dup, "culled_low_opacity": n_low, "culled_too_big": n_big,
@@ -238,8 +262,14 @@ def step_callback(model: SplatfactoDeblurModel, optimizers: Dict[str, torch.opti
     """Call once per training step AFTER backward + optimizer step (what splatfacto registers as its
     AFTER_TRAIN_ITERATION callbacks): accumulates the statistics of the step's render and refines on schedule."""
     # upstream's after_train returns early once densification has stopped: no statistics are gathered any more
-    if step < cfg.stop_split_at and model.xy_grad is not None and model.radii is not None:
-        state.after_backward(model.radii, model.xy_grad, *model.last_size)
+    if cfg.absgrad != state.absgrad:
+        raise ValueError("DensifyConfig.absgrad and DensifyState(absgrad=) disagree")
+    have_stat = (getattr(model, "xy_absgrad", None) if cfg.absgrad else model.xy_grad) is not None
+    if cfg.absgrad and not have_stat and model.xy_grad is not None:
+        raise ValueError("DensifyConfig.absgrad needs model.xy_absgrad: set SplatfactoDeblurConfig.densify_absgrad")
+    if step < cfg.stop_split_at and have_stat and model.radii is not None:
+        state.after_backward(model.radii, model.xy_grad, *model.last_size,
+                             xy_absgrad=getattr(model, "xy_absgrad", None) if cfg.absgrad else None)
     result = None
     if step > cfg.warmup_length and step % cfg.refine_every == 0:
         state.allreduce(group)

@@ -72,6 +72,10 @@ class SplatfactoDeblurConfig:
     # selective_adam's row mask: "visible" = radii > 0 in any sub-pose of any camera of the step (gsplat's rule);
     # "touched" = any non-zero gradient in any Gaussian parameter (what the compositor reached)
     selective_mask: str = "visible"
+    # densification statistic: True = training renders also fill model.xy_absgrad, the per-(pixel, Gaussian) absolute
+    # centre gradient summed over pixels and sub-poses (ops.render_subposes xy_absgrad_out; densify.DensifyConfig.absgrad
+    # reads it).  SE(3) motion model only: the pixel-velocity model refuses it (ValueError)
+    densify_absgrad: bool = False
 
 
 @dataclass
@@ -158,6 +162,9 @@ class SplatfactoDeblurModel(nn.Module):
         # screen-space centre gradient of its backward pass in self.xy_grad [N,2] (pixels)
         self.collect_densify_stats = False
         self.xy_grad: Optional[Tensor] = None
+        # config.densify_absgrad: the absgrad statistic of the same render, same shape(s) as xy_grad
+        self.xy_absgrad: Optional[Tensor] = None
+        self._group_xy_absgrad: Optional[Tensor] = None
         self.last_size = (0, 0)
         # frame-to-frame memory of THIS model's frames (adaptive slice budget, arena estimate): owned here, not by the
         # binding's module state, so two models of one shape never share it
@@ -331,9 +338,11 @@ class SplatfactoDeblurModel(nn.Module):
         means_, scales_, quats_, opac_, dc_, rest_ = gp
         bg = self._background(dev)
         use_gamma = cfg.blur_samples > 0
-        self.xy_grad = None
+        self.xy_grad = self.xy_absgrad = None
         if self.training and self.collect_densify_stats and not detach_gaussians:
             self.xy_grad = torch.zeros(self.num_points, 2, device=dev)
+            if cfg.densify_absgrad:
+                self.xy_absgrad = torch.zeros(self.num_points, 2, device=dev)
         gamma = cfg.gamma if use_gamma else 1.0
         min_level = cfg.min_rgb_level if use_gamma else 0.0
         # one autograd node for composite + gamma-space average: no [S,H,W,3] sample-gradient tensor in backward
@@ -346,7 +355,8 @@ class SplatfactoDeblurModel(nn.Module):
             lin_vel=lin if pixvel else None, ang_vel=ang if pixvel else None,
             times=(list(times) if shared else times_t) if pixvel else None,
             return_depth=want_depth, rolling_shutter_time=self._rs_time(camera) if pixvel else 0.0,
-            sh_rest=rest_, raw_params=True, shared_list=shared, hints=self._hints_of(camera))
+            sh_rest=rest_, raw_params=True, shared_list=shared, hints=self._hints_of(camera),
+            xy_absgrad_out=self.xy_absgrad)
         rgb, alphas, radii = res[:3]
         depth_acc = res[3] if want_depth else None
         self.radii = radii
@@ -385,9 +395,11 @@ class SplatfactoDeblurModel(nn.Module):
         shared = pixvel and cfg.pixel_velocity_lists == "shared"
         bg = self._background(dev)
         use_gamma = cfg.blur_samples > 0
-        self.xy_grad = None
+        self.xy_grad = self.xy_absgrad = None
         if self.training and self.collect_densify_stats:
             self.xy_grad = torch.zeros(self.num_points, 2, device=dev)
+            if cfg.densify_absgrad:
+                self.xy_absgrad = torch.zeros(self.num_points, 2, device=dev)
         cam_leaves = [t for t in (viewmat, lin, ang) if t.requires_grad]
 
         def v_rgb(rgb):
@@ -414,7 +426,7 @@ class SplatfactoDeblurModel(nn.Module):
             sh_rest=self.features_rest, raw_params=True, motion_model=cfg.motion_model, xy_grad_out=self.xy_grad,
             camera_grads=bool(cam_leaves), background_grad=bg.requires_grad,
             rolling_shutter_time=self._rs_time(camera) if pixvel else 0.0, shared_list=shared, hints=self._hints_of(camera),
-            grad_depth=v_depth)
+            grad_depth=v_depth, xy_absgrad_out=self.xy_absgrad)
         for p, gr in ((self.means, g["means"]), (self.scales, g["scales"]), (self.quats, g["quats"]),
                       (self.opacities, g["opacities"]), (self.features_dc, g["sh"]), (self.features_rest, g["sh_rest"])):
             gr = gr.view_as(p)
@@ -472,9 +484,11 @@ class SplatfactoDeblurModel(nn.Module):
         means_, scales_, quats_, opac_, dc_, rest_ = gp
         bg = self._background(dev)
         use_gamma = cfg.blur_samples > 0
-        xy = None
+        xy = xy_abs = None
         if self.training and self.collect_densify_stats and not detach_gaussians:
             xy = torch.zeros(len(items), self.num_points, 2, device=dev)
+            if cfg.densify_absgrad:
+                xy_abs = torch.zeros(len(items), self.num_points, 2, device=dev)
         idx = [c.metadata.get("cam_idx") if c.metadata else None for c, _, _, _ in items]
         hints = self.frame_hints if any(i is None for i in idx) else self.frame_hints.view(("batch",) + tuple(int(i) for i in idx))
         res = ops.render_batch(
@@ -482,7 +496,8 @@ class SplatfactoDeblurModel(nn.Module):
             cam0.height, cam0.width, gamma=cfg.gamma if use_gamma else 1.0,
             min_rgb_level=cfg.min_rgb_level if use_gamma else 0.0, sh_degree=self.active_sh_degree(),
             antialiased=(cfg.rasterize_mode == "antialiased"), return_depth=return_depth, sh_rest=rest_,
-            raw_params=True, xy_grad_out=xy, hints=hints)
+            raw_params=True, xy_grad_out=xy, hints=hints, xy_absgrad_out=xy_abs)
+        self._group_xy_absgrad = xy_abs          # (beside the return value, whose shape callers and tests rely on)
         return res, xy, bg
 
     def get_outputs_batch(self, cameras, detach_gaussians: bool = False,
@@ -492,7 +507,7 @@ class SplatfactoDeblurModel(nn.Module):
         order).  -> {"rgb" [B,H,W,3], "depth" [B,H,W,1] or None, "accumulation" [B,H,W,1], "background"}; when the
         cameras' sizes differ, "rgb" / "depth" / "accumulation" are lists of per-camera tensors instead.
         Training keeps self.radii [B,S*R,N] and self.xy_grad [B,N,2] per camera (lists of per-camera tensors for
-        several groups).  SE(3) motion model only."""
+        several groups), and self.xy_absgrad likewise with config.densify_absgrad.  SE(3) motion model only."""
         cfg = self.config
         if cfg.motion_model != "se3":
             raise NotImplementedError("get_outputs_batch renders the SE(3) motion model; the pixel-velocity model renders "
@@ -502,23 +517,27 @@ class SplatfactoDeblurModel(nn.Module):
             raise ValueError("get_outputs_batch needs at least one camera")
         want_depth = (cfg.output_depth_during_training or not self.training) if return_depth is None else bool(return_depth)
         items, groups = self._batch_groups(cameras)
-        rgb, acc, depth, radii, xys = ([None] * len(cameras) for _ in range(5))
+        rgb, acc, depth, radii, xys, xas = ([None] * len(cameras) for _ in range(6))
         bg = None
         for _, pos in groups:
+            self._group_xy_absgrad = None
             (g_rgb, g_alphas, g_radii, *g_depth), g_xy, bg = self._render_group([items[j] for j in pos], want_depth,
                                                                                 detach_gaussians)
+            g_xa = self._group_xy_absgrad
             g_acc = g_alphas.mean(dim=1)[..., None]
             g_dep = [expected_depth(g_depth[0][k], g_alphas[k]) for k in range(len(pos))] if want_depth else None
             for k, j in enumerate(pos):
                 rgb[j], acc[j], radii[j] = torch.clamp(g_rgb[k], max=1.0), g_acc[k], g_radii[k]
                 depth[j] = g_dep[k] if g_dep is not None else None
                 xys[j] = g_xy[k] if g_xy is not None else None
+                xas[j] = g_xa[k] if g_xa is not None else None
         same = len({tuple(r.shape) for r in rgb}) == 1
         if len(groups) == 1:
             # one frame: the batch's own tensors (its backward writes the xy_grad rows)
-            self.radii, self.xy_grad = g_radii, g_xy
+            self.radii, self.xy_grad, self.xy_absgrad = g_radii, g_xy, g_xa
         else:
             self.radii, self.xy_grad = radii, (None if xys[0] is None else xys)
+            self.xy_absgrad = None if xas[0] is None else xas
         self.last_size = (items[0][0].width, items[0][0].height)
         out = {"background": bg}
         if same:

@@ -292,7 +292,14 @@ def _proj_grad_flags() -> int:
 BWD_SPLAT = int(os.environ.get("GSD_BWD_SPLAT", "0"))
 
 
-def _bwd_variant() -> int:
+# bwd_variant bit GS_BWD_ABSGRAD (include/gsdeblur.h): the absgrad specialisations of the backward compositor
+BWD_ABSGRAD = 2048
+
+
+def _bwd_variant(absgrad: bool = False) -> int:
+    if absgrad:
+        # the absgrad kernels exist for the default compositor only (the splat-parallel measurement form has none)
+        return (256 if (UPSTREAM_GRADS & 4) else 0) | BWD_ABSGRAD
     return (256 if (UPSTREAM_GRADS & 4) else 0) | (1024 if BWD_SPLAT else 0)
 # per-slice emitted intersection counts of the last frame: ints, or 1-element device tensors that are only read back
 # when somebody asks (module attribute `last_slice_intersects`, see __getattr__ below) — the frame itself never waits
@@ -817,9 +824,11 @@ def native_frame_forward(records: Tensor, depth_keys: Tensor, num_tiles_hit: Ten
 
 def native_frame_backward(frame, records: Tensor, bg: Tensor, edges: Tensor, out_T: Tensor, v_img: Tensor,
                           v_alpha: Optional[Tensor], v_records: Tensor, touched: Tensor, combine=None,
-                          v_depth: Optional[Tensor] = None):
+                          v_depth: Optional[Tensor] = None, absgrad: bool = False):
     """v_depth [S,H,W] (optional): d loss / d depth_acc — gs_frame_backward_depth leaves d loss / d record depth in
-    v_records[:, 11]; None issues gs_frame_backward, launch for launch what it always did"""
+    v_records[:, 11]; None issues gs_frame_backward, launch for launch what it always did.
+    absgrad: the absgrad compositors run (bwd_variant + BWD_ABSGRAD) and leave the per-pair absolute centre gradients in
+    v_records[:, 9:11] of every touched row (SE(3) frames only)"""
     L = _L()
     cmb = combine if combine is not None else (None, 1.0, 0.0)
     arena, state = frame["arena"], frame["state"]
@@ -827,7 +836,7 @@ def native_frame_backward(frame, records: Tensor, bg: Tensor, edges: Tensor, out
     relent = lease.arena is None and _arena_relend(frame)
     try:
         _native_frame_backward(L, frame, arena, state, records, bg, edges, out_T, v_img, v_alpha, v_records, touched, cmb,
-                               v_depth)
+                               v_depth, absgrad)
     finally:
         if relent:
             _arena_return(frame)
@@ -838,17 +847,18 @@ def native_frame_backward(frame, records: Tensor, bg: Tensor, edges: Tensor, out
 
 
 def _native_frame_backward(L, frame, arena, state, records, bg, edges, out_T, v_img, v_alpha, v_records, touched, cmb,
-                           v_depth=None):
+                           v_depth=None, absgrad=False):
     L.gs_frame_profile_enable(_profile_mask())
     if v_depth is None:
         st = L.gs_frame_backward(ctypes.byref(state), _ptr(records), _ptr(bg), _ptr(edges), _ptr(out_T), _ptr(v_img),
-                                 _ptr(v_alpha), _ptr(cmb[0]), float(cmb[1]), float(cmb[2]), _bwd_variant(), _ptr(v_records),
-                                 _ptr(touched), _ptr(frame.get("pix_vel")), _ptr(frame.get("sample_times")), _ptr(arena),
+                                 _ptr(v_alpha), _ptr(cmb[0]), float(cmb[1]), float(cmb[2]), _bwd_variant(absgrad),
+                                 _ptr(v_records), _ptr(touched), _ptr(frame.get("pix_vel")), _ptr(frame.get("sample_times")), _ptr(arena),
                                  arena.numel(), _stream())
     else:
         st = L.gs_frame_backward_depth(ctypes.byref(state), _ptr(records), _ptr(bg), _ptr(edges), _ptr(out_T),
                                        _ptr(v_img), _ptr(v_alpha), _ptr(cmb[0]), float(cmb[1]), float(cmb[2]),
-                                       _bwd_variant(), _ptr(v_records), _ptr(touched), _ptr(frame.get("pix_vel")),
+                                       _bwd_variant(absgrad), _ptr(v_records), _ptr(touched),
+                                       _ptr(frame.get("pix_vel")),
                                        _ptr(frame.get("sample_times")), _ptr(arena), arena.numel(), _ptr(v_depth),
                                        _stream())
     if st == 3:
@@ -1184,9 +1194,18 @@ class _RenderSubposes(Function):
     def forward(ctx, means3d, scales, quats, opacities, sh, viewmats, background, S, R, fx, fy, cx, cy,
                 img_height, img_width, sh_degree, antialiased, glob_scale, clip_thresh, xy_grad_out, return_alpha,
                 gamma, min_rgb_level, lin_vel=None, ang_vel=None, times=None, return_depth=False, rs_time=0.0,
-                sh_rest=None, param_flags=0, shared_list=False, hints=None, cameras=1):
+                sh_rest=None, param_flags=0, shared_list=False, hints=None, cameras=1, xy_absgrad_out=None):
         # an output the loss does not use arrives as None in backward instead of a materialised zero tensor
         ctx.set_materialize_grads(False)
+        if xy_absgrad_out is not None:
+            # refused before any device work: the pixel-velocity compositor keeps d loss / d pixel velocity in the tuple
+            # slots absgrad uses, and a test frame backend has no absgrad compositor
+            if times is not None:
+                raise ValueError("xy_absgrad_out is not available with the pixel-velocity model (times=): its backward "
+                                 "compositor uses gradient slots 9 and 10 for d loss / d pixel velocity")
+            if frame_backend is not None and not frame_backend.native_ok():
+                raise ValueError("xy_absgrad_out needs the library's frame path (the absgrad backward compositors); the "
+                                 "frame backend in use has none")
         means3d, scales, quats = _f32(means3d, "means3d"), _f32(scales, "scales"), _f32(quats, "quats")
         opacities, sh = _f32(opacities, "opacities").reshape(-1), _f32(sh, "sh")
         # raw splatfacto parameters (param_flags bit 0: log-scales, bit 1: opacity logits; sh_rest: features_rest beside
@@ -1206,6 +1225,12 @@ class _RenderSubposes(Function):
                 raise ValueError(f"xy_grad_out must be a contiguous float32 {list(xy_shape)} tensor on the Gaussians' "
                                  f"device")
         ctx.xy_grad_out = xy_grad_out
+        if xy_absgrad_out is not None:
+            if (xy_absgrad_out.shape != xy_shape or xy_absgrad_out.dtype != torch.float32
+                    or not xy_absgrad_out.is_contiguous() or xy_absgrad_out.device != means3d.device):
+                raise ValueError(f"xy_absgrad_out must be a contiguous float32 {list(xy_shape)} tensor on the Gaussians' "
+                                 f"device")
+        ctx.xy_absgrad_out = xy_absgrad_out
         N, K = means3d.shape[0], (sh.shape[1] if sh_rest is None else 1 + sh_rest.shape[1])
         P = S * R
         if P > MAX_SUBPOSES:
@@ -1401,7 +1426,7 @@ class _RenderSubposes(Function):
         dev = means3d.device
         L = _L()
         if v_img is None and v_alpha is None and v_depth is None:
-            return (None,) * 33
+            return (None,) * 34
         B = ctx.cameras
         if v_depth is not None:
             # d loss / d depth_acc [S,H,W]: the depth specialisations of the native frame backward (grad flag 64 below)
@@ -1451,7 +1476,12 @@ class _RenderSubposes(Function):
             touched = None
 
         if ctx.frame is not None:
-            native_frame_backward(ctx.frame, records, bg, edges, out_T, v_img, v_al, v_records, touched, combine, v_depth)
+            native_frame_backward(ctx.frame, records, bg, edges, out_T, v_img, v_al, v_records, touched, combine, v_depth,
+                                  ctx.xy_absgrad_out is not None)
+            if ctx.xy_absgrad_out is not None:
+                # camera b's ordered sum over its sub-poses of v_records[:, 9:11], touched rows only; every row stored
+                _check(L.gs_xy_absgrad_sum(N, P, B, _ptr(v_records), _ptr(touched), _ptr(ctx.xy_absgrad_out), _stream()),
+                       "xy_absgrad_sum")
         else:
             ctx.backend.sliced_backward(records, ctx.slices, S, R, H, W, bg, edges, out_T, v_img, v_al, v_records, touched,
                                         combine, ctx.rs)
@@ -1502,7 +1532,7 @@ class _RenderSubposes(Function):
                                               _ptr(psc), psc_n, _stream()), "project_fused_bwd")
         v_bg = (out_T[..., None] * v_img).sum(dim=(0, 1, 2)) if ctx.bg_grad else None
         return ((v_means, v_scales, v_quats, v_opac, v_sh, v_V, v_bg) + (None,) * 16
-                + (v_lin, v_ang, None, None, None, v_sh_rest, None, None, None, None))
+                + (v_lin, v_ang, None, None, None, v_sh_rest, None, None, None, None, None))
 
 
 def render_subposes(means3d: Tensor, scales: Tensor, quats: Tensor, opacities: Tensor, sh: Tensor,
@@ -1513,13 +1543,19 @@ def render_subposes(means3d: Tensor, scales: Tensor, quats: Tensor, opacities: T
                     lin_vel: Optional[Tensor] = None, ang_vel: Optional[Tensor] = None,
                     times: Optional[Tensor] = None, return_depth: bool = False, rolling_shutter_time: float = 0.0,
                     sh_rest: Optional[Tensor] = None, raw_params: bool = False, shared_list: bool = False,
-                    hints: Optional[FrameHints] = None):
+                    hints: Optional[FrameHints] = None, xy_absgrad_out: Optional[Tensor] = None):
     """Fused hot path: project N Gaussians under P=S*R sub-pose viewmats, bin, sort, composite.
     -> (samples [S,H,W,3], alphas [S,H,W], radii int32 [P,N]).  scales/opacities are activated values — or, with
     raw_params=True, splatfacto's RAW parameters: log-scales and opacity logits (exp / sigmoid and their backward run
     inside the projection kernels); sh_rest [N,K-1,3] beside sh = features_dc [N,3] spares the concatenation.
     xy_grad_out (optional float32 [N,2]) is OVERWRITTEN during backward with the sum over the sub-poses of
     the screen-space centre gradient in pixels — what splatfacto's densification reads from ``xys.grad``.
+    xy_absgrad_out (optional float32 [N,2]; SE(3) sub-poses only) is OVERWRITTEN during backward with "absgrad": the
+    sum over the sub-poses and the pixels of |d loss / d x| and |d loss / d y| of each (pixel, Gaussian) pair — the
+    absolute value taken per pair and per component before any sum, so that opposite pushes do not cancel (AbsGS;
+    gsplat's ``means2d.absgrad``).  Rows the frame never touched are 0; either output may be asked for without the
+    other.  It selects the absgrad instantiations of the backward compositor; every other result is bit-identical.
+    The pixel-velocity model (times=) and a test frame backend raise ValueError before any launch.
     return_alpha=False returns None for alphas (as gsplat's rasterize_gaussians does by default).
     Pixel-velocity model (the paper's first-order blur / rolling-shutter model): pass `times` [P] together with
     lin_vel / ang_vel [3] (OpenCV camera frame) and ONE mid-exposure viewmat [4,4] as `viewmats`; every Gaussian is
@@ -1544,7 +1580,7 @@ def render_subposes(means3d: Tensor, scales: Tensor, quats: Tensor, opacities: T
                                 img_height, img_width, sh_degree, antialiased, glob_scale, clip_thresh, xy_grad_out,
                                 bool(return_alpha), None, None, lin_vel, ang_vel, times, bool(return_depth),
                                 float(rolling_shutter_time), sh_rest, 3 if raw_params else 0,
-                                bool(shared_list), hints)
+                                bool(shared_list), hints, 1, xy_absgrad_out)
     return out if return_depth else out[:3]
 
 
@@ -1556,16 +1592,17 @@ def render_combined(means3d: Tensor, scales: Tensor, quats: Tensor, opacities: T
                     return_alpha: bool = True, lin_vel: Optional[Tensor] = None, ang_vel: Optional[Tensor] = None,
                     times: Optional[Tensor] = None, return_depth: bool = False, rolling_shutter_time: float = 0.0,
                     sh_rest: Optional[Tensor] = None, raw_params: bool = False, shared_list: bool = False,
-                    hints: Optional[FrameHints] = None):
+                    hints: Optional[FrameHints] = None, xy_absgrad_out: Optional[Tensor] = None):
     """render_subposes + combine_samples as ONE autograd node: -> (rgb [H,W,3], alphas [S,H,W] or None, radii).
     Same values as the two-step form; the backward skips the [S,H,W,3] per-sample gradient tensor — the
-    compositor's backward derives every pixel's sample gradient from rgb and its gradient."""
+    compositor's backward derives every pixel's sample gradient from rgb and its gradient.
+    xy_absgrad_out: as in render_subposes (float32 [N,2], OVERWRITTEN during backward with the absgrad statistic)."""
     S, R = max(1, int(blur_samples)), max(1, int(rs_bands))
     out = _RenderSubposes.apply(means3d, scales, quats, opacities, sh, viewmats, background, S, R, fx, fy, cx, cy,
                                 img_height, img_width, sh_degree, antialiased, glob_scale, clip_thresh, xy_grad_out,
                                 bool(return_alpha), float(gamma), float(min_rgb_level), lin_vel, ang_vel, times,
                                 bool(return_depth), float(rolling_shutter_time), sh_rest, 3 if raw_params else 0,
-                                bool(shared_list), hints)
+                                bool(shared_list), hints, 1, xy_absgrad_out)
     return out if return_depth else out[:3]
 
 
@@ -1594,7 +1631,7 @@ def render_batch(means3d: Tensor, scales: Tensor, quats: Tensor, opacities: Tens
                  sh_degree: int = 3, antialiased: bool = True, glob_scale: float = 1.0, clip_thresh: float = 0.01,
                  return_alpha: bool = True, return_depth: bool = False, sh_rest: Optional[Tensor] = None,
                  raw_params: bool = False, xy_grad_out: Optional[Tensor] = None, hints: Optional[FrameHints] = None,
-                 times: Optional[Tensor] = None, shared_list: bool = False):
+                 times: Optional[Tensor] = None, shared_list: bool = False, xy_absgrad_out: Optional[Tensor] = None):
     """B cameras in ONE frame and ONE autograd node: render_combined for each camera, with the per-frame costs (launches,
     read-backs) paid once.  viewmats [B, S*R, 4, 4]: camera b's S*R SE(3) sub-pose viewmats in render_combined's order
     (gradients reach them, hence each camera's viewmat and velocities through subpose_viewmats).  The cameras share
@@ -1602,8 +1639,12 @@ def render_batch(means3d: Tensor, scales: Tensor, quats: Tensor, opacities: Tens
     -> (rgb [B,H,W,3], alphas [B,S,H,W] or None, radii int32 [B,S*R,N]) and depth_acc [B,S,H,W] with return_depth.
     xy_grad_out (optional float32 [B,N,2]) is OVERWRITTEN during backward: row b is camera b's sum over its sub-poses
     of the screen-space centre gradient (render_combined's statistic, per camera).
+    xy_absgrad_out (optional float32 [B,N,2]) is OVERWRITTEN during backward: row b is camera b's absgrad statistic
+    (render_subposes), equal to that of camera b rendered alone.
     Limits: B*S*R <= MAX_SUBPOSES and B*S*H*W < 2^30 (check_batch).  The pixel-velocity model (times) and the shared
     list are single-camera forms (NotImplementedError), as is the Python frame backend.  B == 1 is render_combined."""
+    if times is not None and xy_absgrad_out is not None:
+        raise ValueError("xy_absgrad_out is not available with the pixel-velocity model (times=)")
     if times is not None:
         raise NotImplementedError("render_batch renders SE(3) sub-poses; the pixel-velocity model (times=) renders one "
                                   "camera per call (render_combined)")
@@ -1621,17 +1662,21 @@ def render_batch(means3d: Tensor, scales: Tensor, quats: Tensor, opacities: Tens
     N = means3d.shape[0]
     if xy_grad_out is not None and tuple(xy_grad_out.shape) != (B, N, 2):
         raise ValueError(f"xy_grad_out must be [B,N,2] = [{B},{N},2]")
+    if xy_absgrad_out is not None and tuple(xy_absgrad_out.shape) != (B, N, 2):
+        raise ValueError(f"xy_absgrad_out must be [B,N,2] = [{B},{N},2]")
     if B == 1:
         out = _RenderSubposes.apply(means3d, scales, quats, opacities, sh, viewmats[0], background, S, R, fx, fy, cx, cy,
                                     H, W, sh_degree, antialiased, glob_scale, clip_thresh,
                                     None if xy_grad_out is None else xy_grad_out[0], bool(return_alpha), float(gamma),
                                     float(min_rgb_level), None, None, None, bool(return_depth), 0.0, sh_rest,
-                                    3 if raw_params else 0, False, hints)
+                                    3 if raw_params else 0, False, hints, 1,
+                                    None if xy_absgrad_out is None else xy_absgrad_out[0])
     else:
         out = _RenderSubposes.apply(means3d, scales, quats, opacities, sh, viewmats.reshape(B * S * R, 4, 4), background,
                                     B * S, R, fx, fy, cx, cy, H, W, sh_degree, antialiased, glob_scale, clip_thresh,
                                     xy_grad_out, bool(return_alpha), float(gamma), float(min_rgb_level), None, None, None,
-                                    bool(return_depth), 0.0, sh_rest, 3 if raw_params else 0, False, hints, B)
+                                    bool(return_depth), 0.0, sh_rest, 3 if raw_params else 0, False, hints, B,
+                                    xy_absgrad_out)
     rgb, alphas, radii, depth = out
     rgb = rgb.reshape(B, H, W, 3)
     alphas = alphas.reshape(B, S, H, W) if alphas is not None else None

@@ -46,7 +46,8 @@ def render_step(means: Tensor, scales: Tensor, quats: Tensor, opacities: Tensor,
                 motion_model: str = "se3", xy_grad_out: Optional[Tensor] = None, camera_grads: bool = True,
                 background_grad: bool = False, glob_scale: float = 1.0, clip_thresh: float = 0.01,
                 rolling_shutter_time: float = 0.0, shared_list: bool = False, hints: Optional["ops.FrameHints"] = None,
-                grad_depth: Optional[Union[Tensor, Callable[[Tensor, Tensor], Tuple[Tensor, Optional[Tensor]]]]] = None
+                grad_depth: Optional[Union[Tensor, Callable[[Tensor, Tensor], Tuple[Tensor, Optional[Tensor]]]]] = None,
+                xy_absgrad_out: Optional[Tensor] = None
                 ) -> Tuple[Tensor, Dict[str, Optional[Tensor]], Tensor]:
     """One frame, forward and backward.  Arguments as ops.render_combined (raw_params: log-scales / opacity logits;
     sh_rest: features_rest beside sh = features_dc), but the camera comes as ONE mid-exposure `viewmat` [4,4] + body
@@ -58,11 +59,16 @@ def render_step(means: Tensor, scales: Tensor, quats: Tensor, opacities: Tensor,
     depth_acc [S,H,W] (sum over the blended splats of weight * camera-space depth, ops.render_subposes return_depth).
     Either d loss / d depth_acc [S,H,W] as a tensor, or a callable (depth_acc [S,H,W], alphas [S,H,W]) ->
     (d loss / d depth_acc, d loss / d alphas or None), invoked between the two halves like grad_image — a loss on the
-    expected depth depth_acc / alpha needs the alpha term (SplatfactoDeblurModel.render_and_backward does that chain)."""
+    expected depth depth_acc / alpha needs the alpha term (SplatfactoDeblurModel.render_and_backward does that chain).
+    xy_absgrad_out (optional float32 [N,2], motion_model "se3" only): OVERWRITTEN with the absgrad statistic, as in
+    ops.render_subposes; the pixel-velocity model raises ValueError before any launch."""
     S, R = max(1, int(blur_samples)), max(1, int(rs_bands))
     pixvel = motion_model == "pixel_velocity"
     if not pixvel and motion_model != "se3":
         raise ValueError(f"unknown motion_model {motion_model!r}")
+    if pixvel and xy_absgrad_out is not None:
+        raise ValueError("xy_absgrad_out is not available with the pixel-velocity model: its backward compositor uses "
+                         "gradient slots 9 and 10 for d loss / d pixel velocity")
     sub_ctx = None
     if pixvel:
         vms = viewmat
@@ -77,7 +83,7 @@ def render_step(means: Tensor, scales: Tensor, quats: Tensor, opacities: Tensor,
         ctx, means, scales, quats, opacities, sh, vms, background, S, R, fx, fy, cx, cy, img_height, img_width,
         sh_degree, antialiased, glob_scale, clip_thresh, xy_grad_out, depth, float(gamma), float(min_rgb_level),
         lin_vel if pixvel else None, ang_vel if pixvel else None, times if pixvel else None, depth,
-        float(rolling_shutter_time), sh_rest, 3 if raw_params else 0, bool(shared_list), hints)
+        float(rolling_shutter_time), sh_rest, 3 if raw_params else 0, bool(shared_list), hints, 1, xy_absgrad_out)
     if callable(grad_image):
         # the callable may use torch.autograd itself (rgb.requires_grad_() + autograd.grad): it sees a detached leaf and
         # runs with gradient recording on (under this function's no_grad it silently got None)

@@ -432,7 +432,9 @@ def train_scene(model: SplatfactoDeblurModel, scene, images, iterations: int, lr
     if densify is not None:
         from . import densify as D
         model.collect_densify_stats = True
-        state = D.DensifyState(model.num_points, model.means.device)
+        if densify.absgrad and not model.config.densify_absgrad:
+            raise ValueError("DensifyConfig.absgrad needs a model with SplatfactoDeblurConfig.densify_absgrad=True")
+        state = D.DensifyState(model.num_points, model.means.device, densify.absgrad)
         if densify.num_train_data <= 0:
             # upstream's post-reset guard counts in passes over the training images (nerfstudio sets num_train_data
             # from the datamanager); the in-tree trainer knows the number right here

@@ -28,8 +28,14 @@
  *   [14] qx = -log2(e)/2 * conic.x        [15] qz = -log2(e)/2 * conic.z
  *   ([12..15]: per-entry constants of the compositors' validity test |u| <= nmid and of alpha = kmul * 2^u,
  *    u = the exponent of alpha shifted by nmid; written by the projection / gs_pack_records; opacity < 1/255: nmid = -1)
- * Gradient records / tuples: 12 floats, slots 0..8 of the same layout (9, 10: d loss / d pixel velocity; 11: d loss /
- * d depth when a depth gradient is present, gs_frame_backward_depth).
+ * Gradient records / tuples: 12 floats, slots 0..8 of the same layout; 11: d loss / d depth when a depth gradient is
+ * present (gs_frame_backward_depth).  Slots 9 and 10 depend on the compositor that wrote them:
+ *   exact rolling shutter / shared list (gs_rasterize_bwd_rs_slice): d loss / d pixel velocity (x, y), read by
+ *     gs_project_pixvel_bwd with grad flag 16;
+ *   SE(3) compositors with bwd_variant bit GS_BWD_ABSGRAD: "absgrad", the sums over the pixels of |d loss / d x| and
+ *     |d loss / d y| of each (pixel, Gaussian) pair — the absolute value taken per pair and per component BEFORE any
+ *     sum — read by gs_xy_absgrad_sum alone (the projection backwards ignore them);
+ *   SE(3) compositors without that bit: unwritten, and nobody reads their sums.
  */
 #ifndef GSDEBLUR_H
 #define GSDEBLUR_H
@@ -37,6 +43,13 @@
 #ifdef __cplusplus
 extern "C" {
 #endif
+
+/* bwd_variant bit of gs_rasterize_bwd_slice / gs_frame_backward / gs_frame_backward_depth: run the absgrad
+ * specialisations of the backward compositor (tuple form, otherwise-default variant: + 256 is allowed, the round-1 and
+ * splat-parallel forms are refused; SE(3) frames only).  A variant bit and not a sibling entry point: the request changes
+ * which compositor instantiation runs and nothing else — no new argument travels with it — which is what the variant
+ * word already selects, so every existing prototype stays as it is. */
+#define GS_BWD_ABSGRAD 2048
 
 const char* gs_version(void);
 
@@ -473,7 +486,8 @@ int gs_rasterize_bwd_slice(const float* records, const int* sorted_vals, const i
                            const int* sorted_ids /*as in gs_rasterize_fwd_slice*/, int n_records,
                            const unsigned char* tile_hot /*as in gs_rasterize_fwd_slice (same slice)*/,
                            int variant /*0 (2: round-1 kernel, test library only); + 256: upstream alpha-clamp
-                                         gradient, as in gs_rasterize_bwd*/,
+                                         gradient, as in gs_rasterize_bwd; + GS_BWD_ABSGRAD (tuple form only): tuple
+                                         slots 9 and 10 of every flagged tuple receive the entry's absgrad sums*/,
                            const float* cmb_scale /*[H,W,3] or NULL.  Non-NULL folds gs_combine_bwd into this launch:
                                                     v_img then holds the SAMPLE IMAGES [S,H,W,3] and each pixel derives
                                                     its sample gradient from cmb_scale (gs_combine_bwd_scale)*/,
@@ -658,6 +672,12 @@ int gs_frame_backward_depth(const gs_frame_state* state, const float* records, c
                             const float* cmb_scale, float cmb_gamma, float cmb_min_level, int bwd_variant,
                             float* v_records, unsigned char* touched, const float* pix_vel, const float* sample_times,
                             void* arena, long long arena_bytes, const float* v_depth /*[S*H*W] or NULL*/, void* stream);
+/* Absgrad output of a frame backward run with bwd_variant + GS_BWD_ABSGRAD: out[b][i] = the sum over camera b's
+ * sub-poses [b*P/cameras, (b+1)*P/cameras), in sub-pose order, of v_records[p*N+i][9..10], rows with touched[p*N+i] only.
+ * Every row of out [cameras,N,2] is stored, zeros included (out may arrive uninitialised).  One ordered launch, no
+ * atomics.  Densification statistic of AbsGS / gsplat's `absgrad`; same unit as v_xy_sum (pixels). */
+int gs_xy_absgrad_sum(int N, int P, int cameras, const float* v_records /*[P*N,12]*/,
+                      const unsigned char* touched /*[P*N]*/, float* out /*[cameras*N*2]*/, void* stream);
 /* measurement only (not thread-safe): HIP events around the stages of the two calls above.  stage_mask bit i enables
  * stage i of {depth_sort, count_scan, slice_plan, slice_count, emit, tile_sort, bin_edges, raster_fwd, slice_sat,
  * raster_bwd, grad_reduce}; gs_frame_profile_read drains the pairs recorded since the last call (synchronising on
