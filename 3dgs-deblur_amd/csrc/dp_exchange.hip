@@ -120,14 +120,18 @@ __global__ __launch_bounds__(256) void dp_scatter_add_dev_kernel(int cap, const 
 
 static bool make_table(int n, float* const* ptrs, const int* widths, DpTable& tb) {
   if (n <= 0 || n > kMaxDpTensors) return false;
-  tb.n = n;
-  int s = 0;
+  int s = 0, k = 0;
   for (int t = 0; t < n; ++t) {
-    if (!ptrs[t] || widths[t] <= 0) return false;
-    tb.ptr[t] = ptrs[t]; tb.width[t] = widths[t]; tb.start[t] = s;
+    if (widths[t] < 0) return false;
+    if (widths[t] == 0) continue;          // an empty tensor (features_rest [N,0,3] at SH degree 0): no payload columns
+    if (!ptrs[t]) return false;
+    tb.ptr[k] = ptrs[t]; tb.width[k] = widths[t]; tb.start[k] = s;
     s += widths[t];
+    ++k;
   }
-  for (int t = n; t < kMaxDpTensors; ++t) { tb.ptr[t] = nullptr; tb.width[t] = 0; tb.start[t] = s; }
+  if (k == 0) return false;
+  tb.n = k;
+  for (int t = k; t < kMaxDpTensors; ++t) { tb.ptr[t] = nullptr; tb.width[t] = 0; tb.start[t] = s; }
   tb.wtot = s;
   return true;
 }

@@ -345,7 +345,8 @@ GS_EXPORT int gs_adam_step(int count, float* const* params, const float* const* 
 // ---------------------------------------------------------------------------------------------------------------
 // row-masked ("selective") multi-tensor Adam: gs_adam_step's arithmetic on the rows r with mask[r] != 0 only.
 // The tensors share N rows, tensor t has width[t] floats per row (3, 3, 4, 1, 3, 45 for the Gaussian groups at SH
-// degree 3: rows do not align to float4).  Work scales with the selected rows, not with N:
+// degree 3: rows do not align to float4; 0 for features_rest at degree 0 — such a tensor is skipped, as gs_adam_step
+// skips an empty one — and 72 at degree 4: any width goes).  Work scales with the selected rows, not with N:
 //   K1 rows_count_kernel    per 4096-row chunk, how many rows are selected                   (reads N bytes)
 //   K2 rows_scan_kernel     ONE block: exclusive scan of the chunk counts + the grand total (kept on the device)
 //   K3 rows_compact_kernel  per chunk, the selected row ids in ascending order (wave ballot + block prefix)
@@ -354,7 +355,6 @@ GS_EXPORT int gs_adam_step(int count, float* const* params, const float* const* 
 // No atomics (every element has exactly one writer), no host read-back, no launch sized by the selected count.
 // ---------------------------------------------------------------------------------------------------------------
 constexpr int kRowsChunk = 4096;            // rows per block of K1 / K3: 16 passes of 256
-constexpr int kRowsMaxWidth = 64;
 constexpr int kRowsUnroll = 4;              // independent elements in flight per thread and pass of K4
 
 struct AdamRowsArgs {
@@ -530,19 +530,23 @@ GS_EXPORT int gs_adam_step_rows(int count, int N, const unsigned char* mask, flo
   AdamRowsArgs a;
   int wmax = 0;
   for (int t = 0; t < count; ++t) {
-    if (widths[t] < 1 || widths[t] > kRowsMaxWidth) return GS_ERR_INVALID;
+    if (widths[t] < 0) return GS_ERR_INVALID;
+    if (widths[t] == 0) continue;                            // an empty tensor ([N,0,3]: its pointers may be null)
     if (N > 0 && (!params[t] || !grads[t] || !exp_avg[t] || !exp_avg_sq[t])) return GS_ERR_INVALID;
     wmax = widths[t] > wmax ? widths[t] : wmax;
   }
-  if (N == 0) return GS_OK;
+  if (N == 0 || wmax == 0) return GS_OK;
   if (!mask) return GS_ERR_INVALID;
   if (!ws || ws_bytes < gs_adam_step_rows_workspace_bytes(N)) return GS_ERR_WORKSPACE;
   const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
+  int k = 0;
   for (int t = 0; t < count; ++t) {
-    a.p[t] = params[t]; a.g[t] = grads[t]; a.m[t] = exp_avg[t]; a.v[t] = exp_avg_sq[t]; a.width[t] = widths[t];
-    a.step_size[t] = (float)((double)lr[t] / bc1);
+    if (widths[t] == 0) continue;
+    a.p[k] = params[t]; a.g[k] = grads[t]; a.m[k] = exp_avg[t]; a.v[k] = exp_avg_sq[t]; a.width[k] = widths[t];
+    a.step_size[k] = (float)((double)lr[t] / bc1);
+    ++k;
   }
-  a.count = count; a.n_rows_all = N; a.beta1 = (float)beta1; a.beta2 = (float)beta2; a.omb1 = (float)(1.0 - beta1);
+  a.count = k; a.n_rows_all = N; a.beta1 = (float)beta1; a.beta2 = (float)beta2; a.omb1 = (float)(1.0 - beta1);
   a.omb2 = (float)(1.0 - beta2); a.eps = (float)eps; a.inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
   const long long chunks = rows_chunks(N);
   int* rows = reinterpret_cast<int*>(ws);

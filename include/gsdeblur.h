@@ -528,7 +528,8 @@ int gs_combine_bwd_scale_batched(int B, int S, long long n, float gamma, const f
 /* ---- data-parallel gradient exchange (no reference counterpart: the reference is single-GPU,
  *      train.py:114-122 passes no device / world-size flags) -------------------------------------------------
  * The Gaussian gradient tensors share the leading dimension N; tensor t has widths[t] floats per row
- * (means 3, scales 3, quats 4, opacities 1, features_dc 3, features_rest 45 at SH degree 3).  `grads` and
+ * (means 3, scales 3, quats 4, opacities 1, features_dc 3, features_rest 45 at SH degree 3; a tensor of width 0 —
+ * features_rest at degree 0 — takes no payload column and its pointer may be null).  `grads` and
  * `widths` are HOST arrays of n_tensors (<= 16) entries; grads[t] are device pointers.
  * A payload row is wtot = sum(widths) floats followed by the row index as an int32 bit pattern. */
 int gs_dp_row_mask(int N, int n_tensors, float* const* grads, const int* widths,
@@ -702,7 +703,8 @@ int gs_adam_step(int count, float* const* params, const float* const* grads, flo
                  float* const* exp_avg_sq, const long long* numel, const float* lr, double beta1, double beta2, double eps,
                  int step, void* stream);
 /* Adam on the rows r of N with mask[r] != 0 only ("selective" Adam: gsplat's SelectiveAdam, Taming-3DGS's sparse
- * optimizer); tensors share N rows, tensor t has widths[t] (1 .. 64) floats per row; count <= 8; params / grads /
+ * optimizer); tensors share N rows, tensor t has widths[t] >= 0 floats per row (0: the tensor is
+ * skipped and its pointers may be null, as gs_adam_step skips numel 0; no upper limit); count <= 8; params / grads /
  * exp_avg / exp_avg_sq / widths / lr: HOST arrays (device pointers in the first four).
  * Masked-off rows: parameter, exp_avg and exp_avg_sq are not written (bit-unchanged), the gradient is ignored.
  * Selected elements get exactly gs_adam_step's arithmetic and roundings (same step / bias-correction scalars):
