@@ -26,6 +26,7 @@ SOURCES = [
     # x*scale + y must round twice, like the torch ops it replaces (tests compare bit for bit)
     ("dp_exchange.hip", ["-ffp-contract=off"]),
     ("train.hip", []),
+    ("mcmc.hip", []),            # 3DGS-MCMC: per-step position noise, relocation correction (mcmc.py)
     ("frame.hip", []),           # host-side frame orchestration (no kernels of its own)
 ]
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-fvisibility=hidden"]

@@ -95,6 +95,8 @@ _SIGS = {
     "gs_adam_step_rows": [_I, _I, _P, _P, _P, _P, _P, _P, _P, ctypes.c_double, ctypes.c_double, ctypes.c_double, _I,
                           _P, _L, _P],
     "gs_visible_rows": [_I, _I, _P, _P, _P],
+    "gs_mcmc_inject_noise": [_I, _P, _P, _P, _P, _F, _L, _L, _P, _P, _P],
+    "gs_mcmc_relocation": [_I, _P, _P, _P, _P, _P, _P],
 }
 _SIGS_LL = {
     "gs_scan_workspace_bytes": [_L],

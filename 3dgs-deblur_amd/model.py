@@ -76,6 +76,10 @@ class SplatfactoDeblurConfig:
     # centre gradient summed over pixels and sub-poses (ops.render_subposes xy_absgrad_out; densify.DensifyConfig.absgrad
     # reads it).  SE(3) motion model only: the pixel-velocity model refuses it (ValueError)
     densify_absgrad: bool = False
+    # 3DGS-MCMC's regularisers (mcmc.py relies on them to let Gaussians die; upstream 0.01 each): the loss gains
+    # opacity_reg * mean(sigmoid(opacities)) + scale_reg * mean(exp(scales)).  0.0: the step is unchanged, nothing is built
+    opacity_reg: float = 0.0
+    scale_reg: float = 0.0
 
 
 @dataclass

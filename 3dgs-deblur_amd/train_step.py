@@ -103,6 +103,25 @@ def scale_regularization(log_scales: Tensor, max_gauss_ratio: float = 10.0) -> T
     return 0.1 * (torch.maximum(ratio, r) - r).mean()
 
 
+def mcmc_regularization(opacity_logits: Tensor, log_scales: Tensor, opacity_reg: float, scale_reg: float) -> Tensor:
+    """3DGS-MCMC's two regularisers (gsplat's MCMC trainer, recollected; upstream uses 0.01 for both):
+    opacity_reg * mean(sigmoid(opacities)) + scale_reg * mean(exp(scales)).  They are what lets Gaussians die."""
+    reg = opacity_logits.new_zeros(())
+    if opacity_reg:
+        reg = reg + opacity_reg * torch.sigmoid(opacity_logits).mean()
+    if scale_reg:
+        reg = reg + scale_reg * torch.exp(log_scales).mean()
+    return reg
+
+
+def _mcmc_reg(model: SplatfactoDeblurModel) -> Optional[Tensor]:
+    """the MCMC regularisers of model.config, or None when both are 0.0 (nothing is built)"""
+    cfg = model.config
+    if not (cfg.opacity_reg or cfg.scale_reg):
+        return None
+    return mcmc_regularization(model.opacities, model.scales, cfg.opacity_reg, cfg.scale_reg)
+
+
 class SelectiveAdam(torch.optim.Optimizer):
     """Selective ("visibility-masked") Adam in plain torch: gsplat's SelectiveAdam / Taming-3DGS's sparse optimizer.
     step(row_mask) runs torch.optim.Adam's update (no weight decay, no amsgrad; state keys and the tensor step count
@@ -298,6 +317,10 @@ def train_step(model: SplatfactoDeblurModel, optimizers: Dict[str, torch.optim.O
             reg = scale_regularization(model.scales)
             reg.backward()
             loss = loss + reg.detach()
+        reg = _mcmc_reg(model)
+        if reg is not None:
+            reg.backward()
+            loss = loss + reg.detach()
     else:
         out = model.get_outputs(camera, return_depth=True) if use_depth else model.get_outputs(camera)
         rgb = out["rgb"].detach()
@@ -306,6 +329,9 @@ def train_step(model: SplatfactoDeblurModel, optimizers: Dict[str, torch.optim.O
             loss = loss + depth_loss(out["depth"], gt_depth, depth_lambda)
         if model.config.use_scale_regularization:
             loss = loss + scale_regularization(model.scales)
+        reg = _mcmc_reg(model)
+        if reg is not None:
+            loss = loss + reg
         loss.backward()
     if allreduce is not None:
         from . import dp
@@ -360,6 +386,9 @@ def _train_step_batch(model: SplatfactoDeblurModel, optimizers, cameras, gt_imag
     loss = torch.stack([l.reshape(()) for l in losses]).mean()
     if model.config.use_scale_regularization:
         loss = loss + scale_regularization(model.scales)
+    reg = _mcmc_reg(model)
+    if reg is not None:
+        loss = loss + reg
     loss.backward()
     if allreduce is not None:
         _dp_allreduce(model, allreduce)
@@ -421,15 +450,19 @@ def train_scene(model: SplatfactoDeblurModel, scene, images, iterations: int, lr
     [H,W,1] or None, indexed like images (data.load_depth); with depth_lambda > 0 every step adds the depth loss.
     batch_size > 1: every step takes that many views of the shuffle (fewer at the end of a pass) as one batch
     (train_step with lists), and the evaluation renders in batches of that size.  optimizer: make_optimizers' choice
-    ("adam" / "selective_adam"; default model.config.optimizer)."""
+    ("adam" / "selective_adam"; default model.config.optimizer).  densify: a densify.DensifyConfig (splatfacto's split /
+    duplicate / cull schedule, driven by the screen-space gradient statistic) or an mcmc.MCMCConfig (fixed-budget
+    relocation + per-step noise; no statistic is collected, collect_densify_stats stays off)."""
     import time
+    from . import mcmc as M
+    use_mcmc = isinstance(densify, M.MCMCConfig)
     optimizers = make_optimizers(model, lr_scale, optimizer=optimizer)
     g = torch.Generator().manual_seed(seed)
     order = []
     history = []
     t0 = time.time()
     state = None
-    if densify is not None:
+    if densify is not None and not use_mcmc:
         from . import densify as D
         model.collect_densify_stats = True
         if densify.absgrad and not model.config.densify_absgrad:
@@ -454,7 +487,9 @@ def train_scene(model: SplatfactoDeblurModel, scene, images, iterations: int, lr
             gd = depths[i] if depths is not None else None
             h = train_step(model, optimizers, scene.cameras[i], images[i], ssim_lambda, gt_depth=gd,
                            depth_lambda=depth_lambda)
-        if densify is not None:
+        if use_mcmc:
+            M.step_callback(model, optimizers, it, densify)
+        elif densify is not None:
             from . import densify as D
             D.step_callback(model, optimizers, state, it, densify)
         if optimize_eval_cameras and scene.eval_indices and it % eval_camera_every == 0:

@@ -719,6 +719,24 @@ long long gs_adam_step_rows_workspace_bytes(int N);
 /* mask[r] = 1 if radii[p*N + r] > 0 for any of the M planes, else 0 (gsplat's visibility rule); radii int32 [M*N]. */
 int gs_visible_rows(int M, int N, const int* radii, unsigned char* mask, void* stream);
 
+/* ---- 3DGS-MCMC densification (Kheradmand et al. 2024; gsplat's MCMCStrategy, formulas recollected from gsplat 1.x
+ * relocation.cu / strategy/ops.py): mcmc.py drives them.  No allocation, no state; both return 0 on success.
+ *
+ * means[r] += Sigma_r * (z_r * gate_r * scaler) for r < N, in place, one launch: Sigma = R(q/|q|) diag(exp(ls))^2 R^T
+ * from the RAW parameters (log-scales [N,3], unnormalised wxyz quaternions [N,4], 16-byte aligned), gate =
+ * 1 / (1 + exp(100 (sigmoid(logit) - 0.005))).  z_r: three standard normals, Box-Muller over the four words of
+ * Philox4x32-10 with counter (r, 0, step_lo, step_hi) and key (seed_lo, seed_hi) — a function of (seed, step, r) alone —
+ * or, when noise_in [N,3] is given, the caller's.  noise_out [N,3] (optional) receives the normals used.  N == 0 is a
+ * no-op. */
+int gs_mcmc_inject_noise(int N, float* means, const float* log_scales, const float* quats, const float* opacity_logits,
+                         float scaler, long long seed, long long step, const float* noise_in, float* noise_out,
+                         void* stream);
+/* per sampled row i < M: new_opacities[i] = 1 - (1 - o)^(1/n), new_scales[i] = scales[i] * o / D with
+ * D = sum_{k<n} C(n,k+1) (-1)^k o'^(k+1) / sqrt(k+1), n = ratios[i] clamped to [1, 51]; opacities [M] and scales [M,3]
+ * in LINEAR units, ratios int32 [M]; D is summed in double.  M == 0 is a no-op. */
+int gs_mcmc_relocation(int M, const float* opacities, const float* scales, const int* ratios, float* new_opacities,
+                       float* new_scales, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,7 +8,7 @@
 Variants follow /root/reference/train.py:29-76: blur_samples 0 = no motion-blur compensation (the baseline),
 5 (the default, train.py:46) and 10 (synthetic sets, train.py:22); --motion-model picks the SE(3) re-projection
 (north_star) or the paper's pixel-velocity model; --optimize-eval-cameras refines the evaluation poses without
-touching the Gaussians (train.py:180-183)."""
+touching the Gaussians (train.py:180-183); --densify adds splatfacto's refinement schedule or 3DGS-MCMC (--cap-max)."""
 import argparse
 import json
 import os
@@ -44,6 +44,10 @@ def main():
                     help="selective_adam: the Gaussian rows step only when a training view reached them")
     ap.add_argument("--selective-mask", default="visible", choices=["visible", "touched"],
                     help="selective_adam's rows: radii > 0 in the step's view (visible) or a non-zero gradient (touched)")
+    ap.add_argument("--densify", default="none", choices=["none", "splatfacto", "mcmc"],
+                    help="splatfacto: split / duplicate / cull on the gradient statistic; mcmc: fixed-budget relocation "
+                         "+ per-step noise (3DGS-MCMC), with both of its regularisers at upstream's 0.01")
+    ap.add_argument("--cap-max", type=int, default=1_000_000, help="--densify mcmc: the hard cap on the Gaussian count")
     ap.add_argument("--out", default="gpurun_out/deblur")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
@@ -70,11 +74,19 @@ def main():
                                         rs_bands=min(8, (scene.cameras[0].height + 15) // 16),
                                         motion_model=args.motion_model, use_scale_regularization=True,
                                         optimizer=args.optimizer, selective_mask=args.selective_mask)
+        dcfg = None
+        if args.densify == "splatfacto":
+            dcfg = gs.densify.DensifyConfig(stop_split_at=int(0.7 * args.iterations),
+                                            stop_screen_size_at=int(0.3 * args.iterations))
+        elif args.densify == "mcmc":
+            cfg.opacity_reg = cfg.scale_reg = 0.01
+            dcfg = gs.mcmc.MCMCConfig(cap_max=args.cap_max, refine_stop_iter=int(0.9 * args.iterations))
         if args.optimize_eval_cameras:
             cfg.camera_optimizer.mode = "SO3xR3"
         model = SD.init_from_seed_points(cfg, xyz, rgb, dev, num_cameras=len(scene.cameras))
         res = gs.training.train_scene(model, scene, images, args.iterations,
-                                      optimize_eval_cameras=args.optimize_eval_cameras, log_every=100)
+                                      optimize_eval_cameras=args.optimize_eval_cameras, log_every=100,
+                                      densify=dcfg)
         name = (f"blur_samples_{bs}" + ("_pixvel" if args.motion_model == "pixel_velocity" else "") +
                 ("" if args.rolling_shutter_time <= 0 else f"_rs_{args.rolling_shutter_mode}"))
         with open(os.path.join(args.out, f"metrics_{name}.json"), "wt") as f:
