@@ -27,6 +27,7 @@ SOURCES = [
     ("dp_exchange.hip", ["-ffp-contract=off"]),
     ("train.hip", []),
     ("mcmc.hip", []),            # 3DGS-MCMC: per-step position noise, relocation correction (mcmc.py)
+    ("bilagrid.hip", []),        # bilateral-grid colour correction: slice fwd / bwd, TV penalty (bilagrid.py)
     ("frame.hip", []),           # host-side frame orchestration (no kernels of its own)
 ]
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-fvisibility=hidden"]

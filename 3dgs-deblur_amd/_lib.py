@@ -97,6 +97,9 @@ _SIGS = {
     "gs_visible_rows": [_I, _I, _P, _P, _P],
     "gs_mcmc_inject_noise": [_I, _P, _P, _P, _P, _F, _L, _L, _P, _P, _P],
     "gs_mcmc_relocation": [_I, _P, _P, _P, _P, _P, _P],
+    "gs_bilagrid_slice_fwd": [_I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
+    "gs_bilagrid_slice_bwd": [_I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _L, _P],
+    "gs_bilagrid_tv_fwd_bwd": [_I, _I, _I, _I, _P, _F, _P, _P, _P, _L, _P],
 }
 _SIGS_LL = {
     "gs_scan_workspace_bytes": [_L],
@@ -108,6 +111,8 @@ _SIGS_LL = {
     "gs_image_loss_workspace_bytes": [_I, _I],
     "gs_adam_step_rows_workspace_bytes": [_I],
     "gs_frame_backward_bytes": [_P],
+    "gs_bilagrid_slice_bwd_workspace_bytes": [_I, _I, _I, _I, _I, _I, _I],
+    "gs_bilagrid_tv_workspace_bytes": [_I, _I, _I, _I],
 }
 
 _lib = None

@@ -16,7 +16,7 @@ The forward/backward rendering surface; the densification step that follows it l
 from __future__ import annotations
 
 from dataclasses import dataclass, field
-from typing import Dict, Optional
+from typing import Dict, Optional, Tuple
 
 import torch
 from torch import Tensor, nn
@@ -80,6 +80,12 @@ class SplatfactoDeblurConfig:
     # opacity_reg * mean(sigmoid(opacities)) + scale_reg * mean(exp(scales)).  0.0: the step is unchanged, nothing is built
     opacity_reg: float = 0.0
     scale_reg: float = 0.0
+    # per-image bilateral-grid colour correction (bilagrid.py; gsplat's lib_bilagrid / splatfacto's use_bilateral_grid):
+    # training renders of a camera that names itself (metadata['cam_idx']) pass through that camera's learned lattice of
+    # affine colour transforms before the loss; evaluation renders never do.  False: no parameter, no optimizer, no launch
+    use_bilateral_grid: bool = False
+    grid_shape: Tuple[int, int, int] = (16, 16, 8)     # (GW, GH, L)
+    bilateral_grid_tv_lambda: float = 10.0             # weight of the total-variation penalty on all grids
 
 
 @dataclass
@@ -160,6 +166,11 @@ class SplatfactoDeblurModel(nn.Module):
             self.velocity_adjustment = nn.Parameter(torch.zeros(num_cameras, 6))
         else:
             self.velocity_adjustment = None
+        if config.use_bilateral_grid:
+            from . import bilagrid
+            self.bilateral_grids = nn.Parameter(bilagrid.identity_grids(num_cameras, config.grid_shape))
+        else:
+            self.bilateral_grids = None
         self.step = 0                        # training iteration (advanced by train_step)
         self.radii: Optional[Tensor] = None
         # densification statistics (densify.py): when enabled, every training render leaves the summed
@@ -314,8 +325,39 @@ class SplatfactoDeblurModel(nn.Module):
         return float(camera.metadata.get("rolling_shutter_time", 0.0))
 
     # -- rendering ---------------------------------------------------------------------
+    # -- bilateral grid ----------------------------------------------------------------
+    def _grid_index(self, camera: Camera, bilateral_grid: Optional[bool]) -> Optional[int]:
+        """the index of the bilateral grid a render of `camera` passes through, or None.  bilateral_grid None: apply iff
+        the model has grids, is training and the camera names itself; True / False force it.  Raises ValueError — before
+        any launch — when the grid is asked for and absent, or cam_idx is outside [0, num_cameras)."""
+        idx = camera.metadata.get("cam_idx") if camera.metadata else None
+        if bilateral_grid is None:
+            bilateral_grid = self.bilateral_grids is not None and self.training and idx is not None
+        if not bilateral_grid:
+            return None
+        if self.bilateral_grids is None:
+            raise ValueError("bilateral_grid=True needs a model built with SplatfactoDeblurConfig.use_bilateral_grid")
+        if idx is None:
+            raise ValueError("bilateral_grid=True needs camera.metadata['cam_idx']")
+        idx = int(idx)
+        if not 0 <= idx < int(self.bilateral_grids.shape[0]):
+            raise ValueError(f"cam_idx {idx} outside [0, {int(self.bilateral_grids.shape[0])}): no bilateral grid for it")
+        return idx
+
     def get_outputs(self, camera: Camera, detach_gaussians: bool = False,
-                    return_depth: Optional[bool] = None) -> Dict[str, Tensor]:
+                    return_depth: Optional[bool] = None, bilateral_grid: Optional[bool] = None) -> Dict[str, Tensor]:
+        """_render's outputs; with the bilateral grid (bilateral_grid None: iff config.use_bilateral_grid, self.training
+        and 'cam_idx' in the camera's metadata) out["rgb"] is the colour-corrected image bilagrid.slice(grids, rgb,
+        cam_idx).  get_outputs_for_camera never corrects."""
+        gi = self._grid_index(camera, bilateral_grid)
+        out = self._render(camera, detach_gaussians, return_depth)
+        if gi is not None:
+            from . import bilagrid
+            out["rgb"] = bilagrid.slice(self.bilateral_grids, out["rgb"], gi)
+        return out
+
+    def _render(self, camera: Camera, detach_gaussians: bool = False,
+                return_depth: Optional[bool] = None) -> Dict[str, Tensor]:
         """detach_gaussians=True renders with the Gaussians as constants: only the camera-side parameters (pose /
         velocity adjustment, background) receive a gradient — what the fork's `--optimize-eval-cameras`
         (/root/reference/train.py:180-183, README.md:197) needs for the evaluation frames.
@@ -505,7 +547,25 @@ class SplatfactoDeblurModel(nn.Module):
         return res, xy, bg
 
     def get_outputs_batch(self, cameras, detach_gaussians: bool = False,
-                          return_depth: Optional[bool] = None) -> Dict:
+                          return_depth: Optional[bool] = None, bilateral_grid: Optional[bool] = None) -> Dict:
+        """_render_batch's outputs; bilateral_grid as in get_outputs, decided per camera: the corrected cameras pass
+        through their grids in ONE bilagrid.slice call when the batch is one tensor, one call each otherwise."""
+        cameras = list(cameras)
+        gis = [self._grid_index(c, bilateral_grid) for c in cameras]
+        out = self._render_batch(cameras, detach_gaussians, return_depth)
+        if any(g is not None for g in gis):
+            from . import bilagrid
+            rgb = out["rgb"]
+            if isinstance(rgb, Tensor) and all(g is not None for g in gis):
+                out["rgb"] = bilagrid.slice(self.bilateral_grids, rgb, gis)
+            else:
+                out["rgb"] = [r if g is None else bilagrid.slice(self.bilateral_grids, r, g) for r, g in zip(rgb, gis)]
+                if isinstance(rgb, Tensor):
+                    out["rgb"] = torch.stack(out["rgb"])
+        return out
+
+    def _render_batch(self, cameras, detach_gaussians: bool = False,
+                      return_depth: Optional[bool] = None) -> Dict:
         """get_outputs for a list of cameras through ops.render_batch: one frame per group of cameras that share
         intrinsics, size, blur samples and row bands (groups in the order of their first camera; outputs in input
         order).  -> {"rgb" [B,H,W,3], "depth" [B,H,W,1] or None, "accumulation" [B,H,W,1], "background"}; when the
@@ -557,7 +617,7 @@ class SplatfactoDeblurModel(nn.Module):
         was = self.training
         self.eval()
         try:
-            return self.get_outputs_batch(cameras)
+            return self.get_outputs_batch(cameras)      # eval mode: never colour-corrected
         finally:
             self.train(was)
 
@@ -567,7 +627,7 @@ class SplatfactoDeblurModel(nn.Module):
         was = self.training
         self.eval()
         try:
-            return self.get_outputs(camera)
+            return self.get_outputs(camera)             # eval mode: never colour-corrected
         finally:
             self.train(was)
 

@@ -114,6 +114,23 @@ def mcmc_regularization(opacity_logits: Tensor, log_scales: Tensor, opacity_reg:
     return reg
 
 
+def _small_params(model: SplatfactoDeblurModel):
+    """the parameters that are not per-Gaussian rows — learnable background, pose / velocity adjustments, bilateral
+    grids: under data parallelism their gradients travel in one small dense bucket"""
+    return [p for p in (model.background_param, model.pose_adjustment, model.velocity_adjustment,
+                        getattr(model, "bilateral_grids", None)) if p is not None]
+
+
+def _grid_tv(model: SplatfactoDeblurModel) -> Optional[Tensor]:
+    """bilateral_grid_tv_lambda * tv(all grids) as a differentiable loss term, or None without grids / with lambda 0"""
+    grids = getattr(model, "bilateral_grids", None)
+    lam = float(model.config.bilateral_grid_tv_lambda) if grids is not None else 0.0
+    if grids is None or lam == 0.0:
+        return None
+    from . import bilagrid
+    return bilagrid.tv_loss(grids, lam)
+
+
 def _mcmc_reg(model: SplatfactoDeblurModel) -> Optional[Tensor]:
     """the MCMC regularisers of model.config, or None when both are 0.0 (nothing is built)"""
     cfg = model.config
@@ -204,6 +221,10 @@ def make_optimizers(model: SplatfactoDeblurModel, lr_scale: float = 1.0,
         opts["camera_velocity_opt"] = Adam([model.velocity_adjustment], lr=1e-3 * lr_scale, eps=1e-15)
     if model.background_param is not None:
         opts["background"] = Adam([model.background_param], lr=1e-3 * lr_scale, eps=1e-15)
+    if model.bilateral_grids is not None:
+        # splatfacto's bilateral_grid group (2e-3, eps 1e-15); upstream warms it up and decays it — this trainer has no
+        # schedulers
+        opts["bilateral_grid"] = Adam([model.bilateral_grids], lr=2e-3 * lr_scale, eps=1e-15)
     return opts
 
 
@@ -299,10 +320,21 @@ def train_step(model: SplatfactoDeblurModel, optimizers: Dict[str, torch.optim.O
         # kernel's forward already produces d loss / d rgb, so it sits between the two halves as a plain callable
         from . import fused
         box = {}
+        grid_index = model._grid_index(camera, None)       # raises on a bad cam_idx before anything is launched
 
         def grad_image(rgb):
-            box["loss"], v, _ = fused.image_loss_with_grad(rgb, gt_image, ssim_lambda)
-            return v
+            if grid_index is None:
+                box["loss"], v, _ = fused.image_loss_with_grad(rgb, gt_image, ssim_lambda)
+                return v
+            # slice forward -> loss on the corrected image -> slice backward: d loss / d raw rgb goes back to the
+            # compositor, the grid gradient stays on the parameter
+            from . import bilagrid
+            grids = model.bilateral_grids
+            box["rgb"] = corrected = bilagrid.slice_fwd(grids, rgb, grid_index)
+            box["loss"], v, _ = fused.image_loss_with_grad(corrected, gt_image, ssim_lambda)
+            v_rgb, v_grids = bilagrid.slice_bwd(grids, rgb, grid_index, v)
+            grids.grad = v_grids if grids.grad is None else grids.grad + v_grids
+            return v_rgb
         grad_depth = None
         if use_depth:
             def grad_depth(depth, _accumulation):
@@ -310,6 +342,7 @@ def train_step(model: SplatfactoDeblurModel, optimizers: Dict[str, torch.optim.O
                 box["depth_loss"] = dl = depth_loss(depth, gt_depth, depth_lambda)
                 return torch.autograd.grad(dl, depth)[0]
         rgb = model.render_and_backward(camera, grad_image, grad_depth)
+        rgb = box.get("rgb", rgb)                          # the logged PSNR is of the corrected image
         loss = box["loss"]
         if use_depth:
             loss = loss + box["depth_loss"].detach()
@@ -321,6 +354,13 @@ def train_step(model: SplatfactoDeblurModel, optimizers: Dict[str, torch.optim.O
         if reg is not None:
             reg.backward()
             loss = loss + reg.detach()
+        if model.bilateral_grids is not None and model.config.bilateral_grid_tv_lambda:
+            # value and gradient in one kernel call, the gradient added to the parameter's
+            from . import bilagrid
+            grids = model.bilateral_grids
+            if grids.grad is None:
+                grids.grad = torch.zeros_like(grids)
+            loss = loss + bilagrid.tv_fwd_bwd_hip(grids.detach(), float(model.config.bilateral_grid_tv_lambda), grids.grad)
     else:
         out = model.get_outputs(camera, return_depth=True) if use_depth else model.get_outputs(camera)
         rgb = out["rgb"].detach()
@@ -332,14 +372,16 @@ def train_step(model: SplatfactoDeblurModel, optimizers: Dict[str, torch.optim.O
         reg = _mcmc_reg(model)
         if reg is not None:
             loss = loss + reg
+        tv = _grid_tv(model)
+        if tv is not None:
+            loss = loss + tv
         loss.backward()
     if allreduce is not None:
         from . import dp
         dp.allreduce_gradients(list(model.gauss_params().values()), mode=allreduce, average=True)
         # the parameters that are not per-Gaussian rows (learnable background, pose / velocity adjustments) see
         # only this rank's views too: one small dense bucket, or the replicas drift apart silently
-        small = [p for p in (model.background_param, model.pose_adjustment, model.velocity_adjustment)
-                 if p is not None]
+        small = _small_params(model)
         for p in small:
             if p.grad is None:
                 p.grad = torch.zeros_like(p)
@@ -355,7 +397,7 @@ def train_step(model: SplatfactoDeblurModel, optimizers: Dict[str, torch.optim.O
 def _dp_allreduce(model: SplatfactoDeblurModel, allreduce: str) -> None:
     from . import dp
     dp.allreduce_gradients(list(model.gauss_params().values()), mode=allreduce, average=True)
-    small = [p for p in (model.background_param, model.pose_adjustment, model.velocity_adjustment) if p is not None]
+    small = _small_params(model)
     for p in small:
         if p.grad is None:
             p.grad = torch.zeros_like(p)
@@ -389,6 +431,9 @@ def _train_step_batch(model: SplatfactoDeblurModel, optimizers, cameras, gt_imag
     reg = _mcmc_reg(model)
     if reg is not None:
         loss = loss + reg
+    tv = _grid_tv(model)
+    if tv is not None:
+        loss = loss + tv
     loss.backward()
     if allreduce is not None:
         _dp_allreduce(model, allreduce)
@@ -415,7 +460,9 @@ def eval_camera_step(model: SplatfactoDeblurModel, optimizers: Dict[str, torch.o
         return float("nan")
     for o in cam_opts:
         o.zero_grad(set_to_none=True)
-    out = model.get_outputs(camera, detach_gaussians=True)
+    # an evaluation frame has no bilateral grid of its own to learn: rendered without the colour correction
+    no_grid = {"bilateral_grid": False} if getattr(model, "bilateral_grids", None) is not None else {}
+    out = model.get_outputs(camera, detach_gaussians=True, **no_grid)
     gt_image = downscale_image(gt_image, model.downscale_factor())
     loss = image_loss(out["rgb"], gt_image, ssim_lambda)
     loss.backward()

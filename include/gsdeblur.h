@@ -737,6 +737,34 @@ int gs_mcmc_inject_noise(int N, float* means, const float* log_scales, const flo
 int gs_mcmc_relocation(int M, const float* opacities, const float* scales, const int* ratios, float* new_opacities,
                        float* new_scales, void* stream);
 
+/* ---- bilateral-grid colour correction (Chen et al. 2007; per-image learned grids as in gsplat's lib_bilagrid / nerfstudio
+ * splatfacto's use_bilateral_grid, formulas recollected; csrc/bilagrid_math.h): bilagrid.py drives them.  No allocation,
+ * no state, no float atomics: every sum has a fixed order, two runs agree bit for bit.
+ *
+ * grids [G,12,L,GH,GW] fp32, the 12 channels a row-major 3x4 affine [A | b]; GW, GH, L >= 2.  grid_idx int32 [B] (device)
+ * names each image's grid; two images may share one; an index outside [0, G) passes its image through unchanged (out =
+ * rgb, v_rgb = v_out, no grid gradient).  Pixel (x, y) of image b samples its grid at ((x + 0.5) / W, (y + 0.5) / H,
+ * 0.299 r + 0.587 g + 0.114 b of rgb), each clamped to [0, 1], trilinear with align_corners semantics, and out = A rgb + b.
+ * rgb, out, v_out, v_rgb [B,H,W,3].  Any H, W >= 1.  B == 0 or G == 0 is a no-op.  Returns 1 when no tile of the frame
+ * fits its lattice footprint in LDS (L beyond about 190). */
+int gs_bilagrid_slice_fwd(int B, int H, int W, int G, int GW, int GH, int L, const float* grids, const int* grid_idx,
+                          const float* rgb, float* out, void* stream);
+/* scratch of gs_bilagrid_slice_bwd: one partial row per workgroup (7 MB at 1080p with the 16x16x8 grid); -1 on invalid
+ * arguments */
+long long gs_bilagrid_slice_bwd_workspace_bytes(int B, int H, int W, int G, int GW, int GH, int L);
+/* v_rgb = d loss / d rgb (through A and through the guide, the latter zero where the guide left (0, 1)); v_grids
+ * [G,12,L,GH,GW] = d loss / d grids: EVERY value is stored, zeros included for grids no image selected (v_grids may arrive
+ * uninitialised).  ws: 16-byte aligned, gs_bilagrid_slice_bwd_workspace_bytes of the same arguments. */
+int gs_bilagrid_slice_bwd(int B, int H, int W, int G, int GW, int GH, int L, const float* grids, const int* grid_idx,
+                          const float* rgb, const float* v_out, float* v_rgb, float* v_grids, void* ws,
+                          long long ws_bytes, void* stream);
+/* loss_out[0] (device) = weight * tv(grids), tv = 2 (m_x + m_y + m_z) with m_a the mean over images, channels and
+ * positions of the squared forward difference along lattice axis a; v_grids += weight * d tv / d grids (NULL: value
+ * only).  The value is summed in double.  ws: 8-byte aligned.  G == 0 is a no-op. */
+long long gs_bilagrid_tv_workspace_bytes(int G, int GW, int GH, int L);
+int gs_bilagrid_tv_fwd_bwd(int G, int GW, int GH, int L, const float* grids, float weight, float* loss_out,
+                           float* v_grids, void* ws, long long ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

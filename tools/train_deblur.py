@@ -8,7 +8,8 @@
 Variants follow /root/reference/train.py:29-76: blur_samples 0 = no motion-blur compensation (the baseline),
 5 (the default, train.py:46) and 10 (synthetic sets, train.py:22); --motion-model picks the SE(3) re-projection
 (north_star) or the paper's pixel-velocity model; --optimize-eval-cameras refines the evaluation poses without
-touching the Gaussians (train.py:180-183); --densify adds splatfacto's refinement schedule or 3DGS-MCMC (--cap-max)."""
+touching the Gaussians (train.py:180-183); --densify adds splatfacto's refinement schedule or 3DGS-MCMC (--cap-max);
+--bilateral-grid learns a per-image colour correction with the scene."""
 import argparse
 import json
 import os
@@ -48,6 +49,9 @@ def main():
                     help="splatfacto: split / duplicate / cull on the gradient statistic; mcmc: fixed-budget relocation "
                          "+ per-step noise (3DGS-MCMC), with both of its regularisers at upstream's 0.01")
     ap.add_argument("--cap-max", type=int, default=1_000_000, help="--densify mcmc: the hard cap on the Gaussian count")
+    ap.add_argument("--bilateral-grid", action="store_true",
+                    help="per-image bilateral-grid colour correction of the training renders (exposure / white-balance "
+                         "drift); evaluation renders are never corrected")
     ap.add_argument("--out", default="gpurun_out/deblur")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
@@ -73,7 +77,8 @@ def main():
                                         rolling_shutter_mode="exact" if args.rolling_shutter_mode == "exact" else "bands",
                                         rs_bands=min(8, (scene.cameras[0].height + 15) // 16),
                                         motion_model=args.motion_model, use_scale_regularization=True,
-                                        optimizer=args.optimizer, selective_mask=args.selective_mask)
+                                        optimizer=args.optimizer, selective_mask=args.selective_mask,
+                                        use_bilateral_grid=args.bilateral_grid)
         dcfg = None
         if args.densify == "splatfacto":
             dcfg = gs.densify.DensifyConfig(stop_split_at=int(0.7 * args.iterations),
