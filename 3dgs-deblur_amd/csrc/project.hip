@@ -38,7 +38,7 @@ __global__ void subpose_fwd_kernel(int P, const float* __restrict__ V0, const fl
 __global__ __launch_bounds__(256) void subpose_bwd_kernel(int P, const float* __restrict__ V0, const float* __restrict__ lin,
                                    const float* __restrict__ ang, const float* __restrict__ times,
                                    const float* __restrict__ v_out, float* __restrict__ v_V0,
-                                   float* __restrict__ v_lin, float* __restrict__ v_ang) {
+                                   float* __restrict__ v_lin, float* __restrict__ v_ang, int store) {
   typedef Dual<1> D;
   extern __shared__ float sp_part[];          // [P][18]
   for (int gid = threadIdx.x; gid < P * 18; gid += blockDim.x) {
@@ -60,8 +60,11 @@ __global__ __launch_bounds__(256) void subpose_bwd_kernel(int P, const float* __
     float sum = 0.f;
     for (int p = 0; p < P; ++p) sum += sp_part[p * 18 + t];
     float* dst = t < 12 ? v_V0 + t : (t < 15 ? v_lin + (t - 12) : v_ang + (t - 15));
-    *dst += sum;                               // (accumulating contract: the caller zeroes; single writer)
+    // (accumulating contract: the caller zeroes; single writer.  store: the sum lands on +0 instead of on what the
+    //  caller left there — the same bits as accumulating into a zeroed buffer, without the caller's fill launch)
+    *dst = (store ? 0.f : *dst) + sum;
   }
+  if (store && threadIdx.x >= 18 && threadIdx.x < 22) v_V0[threadIdx.x - 6] = 0.f;     // row 3 of v_viewmat
 }
 
 // ---------------------------------------------------------------------------
@@ -118,7 +121,8 @@ __device__ __forceinline__ void reduce_vV(const float vV[12], float* __restrict_
 
 // partial [nblocks][slots][12] (every row written by its block) -> dst(slot)[0..11] += sum over the blocks, in order:
 // thread t adds rows t, t + 256, ... ; the 256 partial sums then go through a fixed tree.  One block per slot.
-struct PoseDst { float* slot0; float* slot1; int stride; };   // slot s -> (s == 1 && slot1) ? slot1 : slot0 + s * stride
+struct PoseDst { float* slot0; float* slot1; int stride; int store; };   // slot s -> (s == 1 && slot1) ? slot1 : slot0 + s * stride;
+                                                   // store: dst = +0 + sum (the caller hands over uninitialised rows of 16: floats 12..15 = 0)
 __global__ __launch_bounds__(256) void pose_reduce_kernel(const float* __restrict__ partial, int nblocks, int slots,
                                                           PoseDst dst) {
   __shared__ double red[256][13];              // (double: the rows are fp32 block sums; adding thousands of them costs nothing)
@@ -142,7 +146,8 @@ __global__ __launch_bounds__(256) void pose_reduce_kernel(const float* __restric
       for (int j = 0; j < 12; ++j) red[threadIdx.x][j] += red[threadIdx.x + w][j];
     __syncthreads();
   }
-  if (threadIdx.x < 12) out[threadIdx.x] += (float)red[0][threadIdx.x];
+  if (threadIdx.x < 12) out[threadIdx.x] = (dst.store ? 0.f : out[threadIdx.x]) + (float)red[0][threadIdx.x];
+  else if (dst.store && threadIdx.x < 16) out[threadIdx.x] = 0.f;
 }
 
 __global__ __launch_bounds__(256) void project_bwd_kernel(int N, const float* __restrict__ means,
@@ -500,6 +505,8 @@ struct FusedOut {
   float* v_xy_sum;        // [N,2] or null
   float* v_twist;         // [12] accumulated, pixel-velocity model, may be null
   float* pose_partial;    // scratch [blocks][slots][12] of the ordered pose-gradient reduction (with v_viewmats / v_twist)
+  unsigned char* dirty;   // [N] or null: the pooled mode of the sparse launch (see project_fused_bwd_sparse_kernel)
+  int clear_touched;      // the sparse kernel is the call's last reader of `touched`: it clears the flags it found set
 };
 
 // DEPTH (grad flag 64): v_records[.., 11] is d loss / d z, z = the record's camera-space depth — under sub-pose p's
@@ -783,13 +790,29 @@ __device__ __forceinline__ void needle_item_pixvel(const FusedParams& fp, const 
 // order (deterministic) before it runs the covariance -> scale / quaternion step and writes the three rows.
 constexpr int kNeedleChunk = 2048;
 
+// clear_touched (pooled mode: the needle launch is the call's last reader of `touched`): once every needle item of the
+// block has read its flags (the rounds end on a barrier), the thread stores zeros over the flags set among ITS eight
+// Gaussians — the caller's persistent buffer is all zero again without a fill.  (The words are read a second time: a
+// value kept across the rounds would cost the registers of the kernel's third wave per SIMD.)
+__device__ __noinline__ void needle_clear_touched(int N, int P, unsigned char* touched) {
+  if (!touched) return;
+  const int c0 = blockIdx.x * kNeedleChunk + (int)threadIdx.x * 8;
+  if (c0 >= N) return;
+  const bool word = (N % 8) == 0 && c0 + 8 <= N;
+  for (int p = 0; p < P; ++p) {
+    unsigned char* t = touched + (size_t)p * N + c0;
+    if (word) { unsigned long long* w = reinterpret_cast<unsigned long long*>(t); if (*w != 0ull) *w = 0ull; }
+    else for (int j = 0; j < 8 && c0 + j < N; ++j) if (t[j]) t[j] = 0;
+  }
+}
+
 // ONE source for project_needle_hp_kernel and its depth twin project_needle_hp_depth_kernel (grad flag 64:
 // v_records[.., 11] enters the means' double-precision chain too), instantiated by this macro (default kernel: same name,
 // same instruction stream)
 #define GS_NEEDLE_HP_KERNEL(NAME, DEPTH)                                                                                \
 __global__ __launch_bounds__(256) void NAME(FusedParams fp, const float* __restrict__ records,                          \
     const float* __restrict__ v_records, float* __restrict__ v_means, float* __restrict__ v_scales,                    \
-    float* __restrict__ v_quats, const unsigned char* __restrict__ touched, float ratio_limit) {                       \
+    float* __restrict__ v_quats, unsigned char* __restrict__ touched, float ratio_limit, int clear_touched) {         \
   __shared__ int list[kNeedleChunk];                                                                                          \
   __shared__ int n_list;                                                                                                      \
   __shared__ double part[256][9];                                                                                             \
@@ -821,7 +844,10 @@ __global__ __launch_bounds__(256) void NAME(FusedParams fp, const float* __restr
   }                                                                                                                           \
   __syncthreads();                                                                                                            \
   const int n = n_list;                                                                                                       \
-  if (n == 0) return;                                                                                                         \
+  if (n == 0) {                                                                                                               \
+    if (clear_touched) needle_clear_touched(fp.N, fp.P, touched);                                                                     \
+    return;                                                                                                                   \
+  }                                                                                                                           \
   const int items_per = fp.pixvel ? 1 : fp.P;                  /* <= 256 (kMaxSubposes) */                                    \
   const int per_round = max(1, 256 / items_per);               /* needles per round */                                        \
   for (int base = 0; base < n; base += per_round) {                                                                           \
@@ -852,6 +878,7 @@ _Pragma("unroll")                                                               
     }                                                                                                                         \
     __syncthreads();                                                                                                          \
   }                                                                                                                           \
+  if (clear_touched) needle_clear_touched(fp.N, fp.P, touched);                                                                       \
 }
 
 GS_NEEDLE_HP_KERNEL(project_needle_hp_kernel, false)
@@ -901,59 +928,121 @@ __device__ __forceinline__ void zero_rows(float* __restrict__ base, size_t first
   for (size_t k = head + 4 * n4 + threadIdx.x; k < count; k += blockDim.x) p[k] = 0.f;
 }
 
+// one thread zeroes floats [first, first + count) of `base` (a dirty row: 16-byte stores where the row allows them)
+__device__ __forceinline__ void zero_span(float* __restrict__ base, size_t first, size_t count) {
+  float* p = base + first;
+  size_t k = 0;
+  for (; k < count && (reinterpret_cast<uintptr_t>(p + k) & 15u) != 0; ++k) p[k] = 0.f;
+  for (; k + 4 <= count; k += 4) *reinterpret_cast<float4*>(p + k) = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (; k < count; ++k) p[k] = 0.f;
+}
+
 // (256, 2): two waves per SIMD = at most 256 VGPRs.  The body sits right at that cliff (256 with the round-3 pixel-
 // velocity VJP, 258 with round 4's — one wave per SIMD, and the zero fill of the 236 MB of gradient outputs, which is
 // most of this kernel's time on a sparse frame, dropped from 3.3 to 2.3 TB/s: 72 -> 104 us, found by an on-GPU bisect)
 // ONE source for project_fused_bwd_sparse_kernel and its depth twin project_fused_bwd_sparse_depth_kernel (grad flag 64)
+// The touched flags of the block's eight rounds are all loaded before the first ballot (their latencies overlap instead
+// of adding up; the compaction order — round, wave, lane — is what it was, and with it the order of the pose sums).
+// Pooled mode (ZERO_FILL with out.dirty, gs_project_fused_bwd_pooled): the five (six) gradient arrays are +0.0
+// everywhere except in the rows flagged in dirty[N] — what an earlier call on the same buffers wrote.  The block reads
+// ITS slice of `dirty`, zeroes just those rows (more than a quarter of the chunk dirty: it streams zeros over the whole
+// chunk as the plain ZERO_FILL does — a per-block, deterministic choice with the same result) and stores
+// dirty[g] = (some sub-pose touched g), the rows its body is about to write.  A block reads and writes its own chunk of
+// every array only: no atomics, no order between blocks.  v_xy_sum is the caller's buffer and is streamed as ever.
+// out.clear_touched: see FusedOut.
 #define GS_FUSED_BWD_SPARSE_KERNEL(NAME, DEPTH)                                                                         \
 template <int MAXB, bool ZERO_FILL>                                                                                     \
 __global__ __launch_bounds__(256, 2) void NAME(FusedParams fp,                                                          \
     const float* __restrict__ records, const float* __restrict__ v_records, FusedOut out,                               \
-    const unsigned char* __restrict__ touched /* [P*N] */) {                                                            \
+    unsigned char* __restrict__ touched /* [P*N] */) {                                                                  \
   __shared__ float lds[48];                                                                                               \
   __shared__ int list[kFusedChunk];                                                                                       \
-  __shared__ int wave_cnt[4];                                                                                             \
+  __shared__ int wave_cnt[kFusedChunk / 256][4];                                                                          \
+  __shared__ int n_dirty;                                                                                                 \
   extern __shared__ float blk_acc[];             /* [slots][12]: this block's pose-gradient sums (reduce_vV) */           \
   const int slots = out.pose_partial ? (fp.pixvel ? 2 : fp.P) : 0;                                                        \
   for (int k = threadIdx.x; k < slots * 12; k += 256) blk_acc[k] = 0.f;                                                   \
   const int lane = lane_id(), wave = threadIdx.x >> 6;                                                                    \
   const int base = blockIdx.x * kFusedChunk;                                                                              \
+  const int g_first = base + (int)threadIdx.x;   /* this thread's Gaussian of round r: g_first + 256 r */                 \
+  unsigned any_m = 0u;                           /* bit r: some sub-pose touched it */                                    \
+  for (int p = 0; p < fp.P; ++p) {                                                                                        \
+    const unsigned char* t = touched + (size_t)p * fp.N;                                                                  \
+    unsigned char v[kFusedChunk / 256];                                                                                   \
+_Pragma("unroll")                                                                                                         \
+    for (int r = 0; r < kFusedChunk / 256; ++r) v[r] = t[min(g_first + r * 256, fp.N - 1)];                               \
+_Pragma("unroll")                                                                                                         \
+    for (int r = 0; r < kFusedChunk / 256; ++r) any_m |= (v[r] != 0 && g_first + r * 256 < fp.N) ? (1u << r) : 0u;        \
+  }                                                                                                                       \
   if (ZERO_FILL) {                                                                                                        \
     const size_t g0 = (size_t)base, cnt = (size_t)min(kFusedChunk, fp.N - base);                                          \
-    zero_rows(out.v_means, 3 * g0, 3 * cnt);                                                                              \
-    zero_rows(out.v_scales, 3 * g0, 3 * cnt);                                                                             \
-    zero_rows(out.v_quats, 4 * g0, 4 * cnt);                                                                              \
-    zero_rows(out.v_opac, g0, cnt);                                                                                       \
-    if (out.v_sh_rest) {                                                                                                  \
-      zero_rows(out.v_sh, 3 * g0, 3 * cnt);                                                                               \
-      zero_rows(out.v_sh_rest, (size_t)(fp.K_stride - 1) * 3 * g0, (size_t)(fp.K_stride - 1) * 3 * cnt);                  \
-    } else {                                                                                                              \
-      zero_rows(out.v_sh, (size_t)fp.K_stride * 3 * g0, (size_t)fp.K_stride * 3 * cnt);                                   \
+    const size_t sh_row = out.v_sh_rest ? 3 : (size_t)fp.K_stride * 3, rest_row = (size_t)(fp.K_stride - 1) * 3;         \
+    bool stream = true;                                                                                                   \
+    if (out.dirty) {                                                                                                      \
+      if (threadIdx.x == 0) n_dirty = 0;                                                                                  \
+      __syncthreads();                                                                                                    \
+      unsigned char d[kFusedChunk / 256];                                                                                 \
+_Pragma("unroll")                                                                                                         \
+      for (int r = 0; r < kFusedChunk / 256; ++r) d[r] = out.dirty[min(g_first + r * 256, fp.N - 1)];                     \
+      unsigned dirty_m = 0u;                                                                                              \
+_Pragma("unroll")                                                                                                         \
+      for (int r = 0; r < kFusedChunk / 256; ++r) dirty_m |= (d[r] != 0 && g_first + r * 256 < fp.N) ? (1u << r) : 0u;    \
+      if (dirty_m) atomicAdd(&n_dirty, __popc(dirty_m));                                                                  \
+      __syncthreads();                                                                                                    \
+      stream = (size_t)n_dirty * 4 > cnt;                                                                                 \
+      if (!stream) {                                                                                                      \
+        for (int r = 0; r < kFusedChunk / 256; ++r) {                                                                     \
+          if (!((dirty_m >> r) & 1u)) continue;                                                                           \
+          const size_t g = (size_t)(g_first + r * 256);                                                                   \
+          zero_span(out.v_means, 3 * g, 3);                                                                               \
+          zero_span(out.v_scales, 3 * g, 3);                                                                              \
+          zero_span(out.v_quats, 4 * g, 4);                                                                               \
+          out.v_opac[g] = 0.f;                                                                                            \
+          zero_span(out.v_sh, sh_row * g, sh_row);                                                                        \
+          if (out.v_sh_rest) zero_span(out.v_sh_rest, rest_row * g, rest_row);                                            \
+        }                                                                                                                 \
+      }                                                                                                                   \
+      /* the map of what this call leaves behind: the rows of the touched Gaussians, written by the body below */         \
+      for (int r = 0; r < kFusedChunk / 256; ++r)                                                                         \
+        if (((dirty_m ^ any_m) >> r) & 1u) out.dirty[g_first + r * 256] = (unsigned char)((any_m >> r) & 1u);             \
+    }                                                                                                                     \
+    if (stream) {                                                                                                         \
+      zero_rows(out.v_means, 3 * g0, 3 * cnt);                                                                            \
+      zero_rows(out.v_scales, 3 * g0, 3 * cnt);                                                                           \
+      zero_rows(out.v_quats, 4 * g0, 4 * cnt);                                                                            \
+      zero_rows(out.v_opac, g0, cnt);                                                                                     \
+      zero_rows(out.v_sh, sh_row * g0, sh_row * cnt);                                                                     \
+      if (out.v_sh_rest) zero_rows(out.v_sh_rest, rest_row * g0, rest_row * cnt);                                         \
     }                                                                                                                     \
     zero_rows(out.v_xy_sum, 2 * g0, 2 * cnt);                                                                             \
     /* the rows of this block's touched Gaussians are written again below, by other threads of the block */               \
     __threadfence_block();                                                                                                \
   }                                                                                                                       \
-  int n_list = 0;                                                                                                         \
+_Pragma("unroll")                                                                                                         \
   for (int r = 0; r < kFusedChunk / 256; ++r) {                                                                           \
-    const int g = base + r * 256 + (int)threadIdx.x;                                                                      \
-    bool any = false;                                                                                                     \
-    if (g < fp.N)                                                                                                         \
-      for (int p = 0; p < fp.P; ++p) any |= touched[(size_t)p * fp.N + g] != 0;                                           \
+    const unsigned long long bal = __ballot((any_m >> r) & 1u);                                                           \
+    if (lane == 0) wave_cnt[r][wave] = __popcll(bal);                                                                     \
+  }                                                                                                                       \
+  __syncthreads();                                                                                                        \
+  int n_list = 0;                                                                                                         \
+_Pragma("unroll")                                                                                                         \
+  for (int r = 0; r < kFusedChunk / 256; ++r) {                                                                           \
+    const bool any = (any_m >> r) & 1u;                                                                                   \
     const unsigned long long bal = __ballot(any);                                                                         \
-    if (lane == 0) wave_cnt[wave] = __popcll(bal);                                                                        \
-    __syncthreads();                                                                                                      \
     int off = n_list, total = 0;                                                                                          \
 _Pragma("unroll")                                                                                                         \
-    for (int w = 0; w < 4; ++w) { const int c = wave_cnt[w]; if (w < wave) off += c; total += c; }                        \
-    if (any) list[off + __popcll(bal & ((1ull << lane) - 1ull))] = g;                                                     \
+    for (int w = 0; w < 4; ++w) { const int c = wave_cnt[r][w]; if (w < wave) off += c; total += c; }                     \
+    if (any) list[off + __popcll(bal & ((1ull << lane) - 1ull))] = g_first + r * 256;                                     \
     n_list += total;                                                                                                      \
-    __syncthreads();                                                                                                      \
   }                                                                                                                       \
+  __syncthreads();                                                                                                        \
   for (int k0 = 0; k0 < n_list; k0 += 256) {                                                                              \
     const int k = k0 + (int)threadIdx.x;                                                                                  \
     const bool live = k < n_list;                                                                                         \
     fused_bwd_body<MAXB, DEPTH>(fp, records, v_records, out, touched, live ? list[k] : 0, live, lds, blk_acc);            \
+    /* (a thread's body reads the flags of its own Gaussian only) */                                                      \
+    if (out.clear_touched && live)                                                                                        \
+      for (int p = 0; p < fp.P; ++p) touched[(size_t)p * fp.N + list[k]] = 0;                                             \
   }                                                                                                                       \
   __syncthreads();                                                                                                        \
   for (int k = threadIdx.x; k < slots * 12; k += 256) out.pose_partial[(size_t)blockIdx.x * slots * 12 + k] = blk_acc[k]; \
@@ -1109,7 +1198,18 @@ GS_EXPORT int gs_subpose_viewmats_bwd(int P, const float* viewmat, const float* 
                                       float* v_ang, void* stream) {
   if (P <= 0) return GS_ERR_INVALID;
   hipLaunchKernelGGL(subpose_bwd_kernel, dim3(1), dim3(256), (size_t)P * 18 * sizeof(float), (hipStream_t)stream, P, viewmat, lin_vel,
-                     ang_vel, times, v_out, v_viewmat, v_lin, v_ang);
+                     ang_vel, times, v_out, v_viewmat, v_lin, v_ang, 0);
+  return gs_launch_status();
+}
+
+// The same sums STORED: v_viewmat[16] (row 3 = 0), v_lin[3], v_ang[3] may be uninitialised — every float is written,
+// with the bits gs_subpose_viewmats_bwd leaves in zeroed buffers (the kernel is one block and owns its accumulators).
+GS_EXPORT int gs_subpose_viewmats_bwd_store(int P, const float* viewmat, const float* lin_vel, const float* ang_vel,
+                                            const float* times, const float* v_out, float* v_viewmat, float* v_lin,
+                                            float* v_ang, void* stream) {
+  if (P <= 0 || !v_viewmat || !v_lin || !v_ang) return GS_ERR_INVALID;
+  hipLaunchKernelGGL(subpose_bwd_kernel, dim3(1), dim3(256), (size_t)P * 18 * sizeof(float), (hipStream_t)stream, P, viewmat, lin_vel,
+                     ang_vel, times, v_out, v_viewmat, v_lin, v_ang, 1);
   return gs_launch_status();
 }
 
@@ -1145,7 +1245,7 @@ GS_EXPORT int gs_project_bwd(int N, const float* means, const float* scales, flo
                      rows, grad_flags);
   if (v_viewmat)
     hipLaunchKernelGGL(pose_reduce_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, rows, blocks, 1,
-                       PoseDst{v_viewmat, nullptr, 0});
+                       PoseDst{v_viewmat, nullptr, 0, 0});
   return gs_launch_status();
 }
 
@@ -1296,8 +1396,15 @@ static long long pose_scratch_bytes(int N, int P, bool pixvel, bool with_touched
 }
 
 static int launch_fused_bwd(const FusedParams& fp, int sh_degree, const float* records, const float* v_records,
-                            FusedOut out, const unsigned char* touched, void* scratch, long long scratch_bytes,
-                            hipStream_t st) {
+                            FusedOut out, const unsigned char* touched_in, void* scratch, long long scratch_bytes,
+                            hipStream_t st, int clear_touched = 0) {
+  // clear_touched (pooled mode): the call's last launch that reads `touched` clears the flags it found set — 1: the last
+  // one of this function's launches (the needle kernel, or the sparse kernel when there is none), 2: a later launch of
+  // the caller's does; 0: the flags are left as they are (and nothing here writes to them)
+  unsigned char* touched = const_cast<unsigned char*>(touched_in);
+  const bool needles = !(fp.flags & GS_FLAG_NO_NEEDLE_HP);
+  out.clear_touched = (clear_touched == 1 && !needles) ? 1 : 0;
+  const int needle_clears = (clear_touched == 1 && needles) ? 1 : 0;
   dim3 block(256);
   const int N = fp.N;
   const bool pose = out.v_viewmats || out.v_twist;
@@ -1341,18 +1448,18 @@ static int launch_fused_bwd(const FusedParams& fp, int sh_degree, const float* r
   if (pose) {
     // the blocks' rows, added up in block order: v_viewmats[p] (SE(3): one slot per sub-pose, 16 floats apart), or
     // v_viewmat and v_twist (pixel-velocity model: slots 0 and 1)
-    PoseDst dst{out.v_viewmats, fp.pixvel ? out.v_twist : nullptr, fp.pixvel ? 0 : 16};
+    PoseDst dst{out.v_viewmats, fp.pixvel ? out.v_twist : nullptr, fp.pixvel ? 0 : 16, (!fp.pixvel && out.dirty) ? 1 : 0};
     hipLaunchKernelGGL(pose_reduce_kernel, dim3(slots), dim3(256), 0, st, out.pose_partial, (int)grid.x, slots, dst);
   }
-  if (!(fp.flags & GS_FLAG_NO_NEEDLE_HP))
+  if (needles)
     // needles (scale ratio above kNeedleRatio) get their means / scales / quaternion gradients again, in double
   {
     if (depth)
       hipLaunchKernelGGL(project_needle_hp_depth_kernel, dim3((N + kNeedleChunk - 1) / kNeedleChunk), dim3(256), 0, st, fp,
-                         records, v_records, out.v_means, out.v_scales, out.v_quats, touched, kNeedleRatio);
+                         records, v_records, out.v_means, out.v_scales, out.v_quats, touched, kNeedleRatio, needle_clears);
     else
       hipLaunchKernelGGL(project_needle_hp_kernel, dim3((N + kNeedleChunk - 1) / kNeedleChunk), dim3(256), 0, st, fp,
-                         records, v_records, out.v_means, out.v_scales, out.v_quats, touched, kNeedleRatio);
+                         records, v_records, out.v_means, out.v_scales, out.v_quats, touched, kNeedleRatio, needle_clears);
   }
   return gs_launch_status();
 }
@@ -1362,8 +1469,8 @@ static int launch_fused_bwd(const FusedParams& fp, int sh_degree, const float* r
 // the sum fused_bwd_body forms for a single camera (vxs / vys), in the same order, so camera b's row equals that of
 // camera b rendered alone given the same v_records.  One thread per Gaussian, all B rows written (zeros included).
 __global__ __launch_bounds__(256) void xy_grad_cams_kernel(int N, int P, int B, const float* __restrict__ v_records,
-                                                           const unsigned char* __restrict__ touched,
-                                                           float* __restrict__ v_xy) {
+                                                           unsigned char* __restrict__ touched,
+                                                           float* __restrict__ v_xy, int clear_touched) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= N) return;
   const int Pc = P / B;
@@ -1372,6 +1479,7 @@ __global__ __launch_bounds__(256) void xy_grad_cams_kernel(int N, int P, int B, 
     for (int p = b * Pc; p < (b + 1) * Pc; ++p) {
       const size_t idx = (size_t)p * N + i;
       if (!touched[idx]) continue;
+      if (clear_touched) touched[idx] = 0;      // (pooled mode: the call's last reader, see launch_fused_bwd)
       const float2 g = *reinterpret_cast<const float2*>(v_records + idx * kGradFloats);
       vxs += g.x; vys += g.y;
     }
@@ -1420,15 +1528,15 @@ GS_EXPORT long long gs_project_pose_scratch_bytes(int N, int P, int with_touched
 // pose_scratch of gs_project_pose_scratch_bytes(N, P, touched != NULL) bytes: the sum over the Gaussians is ordered).
 // grad_flags: 1 = back-propagate through the fov clamp as upstream gsplat 0.1.11 does (as if inactive), 2 = return
 // the quaternion gradient without the projection through q/|q| (deviations 2 and 3).
-GS_EXPORT int gs_project_fused_bwd(int N, int P, const float* means, const float* scales, float glob_scale,
-                                   const float* quats, const float* opacities, const float* sh, int K_stride,
-                                   int sh_degree, const float* viewmats, float fx, float fy, float cx, float cy,
-                                   int H, int W, float clip, int antialiased, const float* records,
-                                   const float* v_records, float* v_means, float* v_scales, float* v_quats,
-                                   float* v_opacities, float* v_sh, float* v_viewmats,
-                                   const unsigned char* touched, float* v_xy_sum, int grad_flags, const float* sh_rest,
-                                   int param_flags, float* v_sh_rest, void* pose_scratch, long long pose_scratch_bytes_,
-                                   void* stream) {
+static int project_fused_bwd_impl(int N, int P, const float* means, const float* scales, float glob_scale,
+                                  const float* quats, const float* opacities, const float* sh, int K_stride,
+                                  int sh_degree, const float* viewmats, float fx, float fy, float cx, float cy,
+                                  int H, int W, float clip, int antialiased, const float* records,
+                                  const float* v_records, float* v_means, float* v_scales, float* v_quats,
+                                  float* v_opacities, float* v_sh, float* v_viewmats,
+                                  const unsigned char* touched, float* v_xy_sum, int grad_flags, const float* sh_rest,
+                                  int param_flags, float* v_sh_rest, void* pose_scratch, long long pose_scratch_bytes_,
+                                  void* stream, unsigned char* dirty) {
   if (N <= 0 || P <= 0 || sh_degree < 0 || sh_degree > 4 || (sh_degree + 1) * (sh_degree + 1) > K_stride ||
       (sh_rest != nullptr) != (v_sh_rest != nullptr) || ((grad_flags & GS_FLAG_ZERO_FILL) && !touched))
     return GS_ERR_INVALID;
@@ -1442,13 +1550,52 @@ GS_EXPORT int gs_project_fused_bwd(int N, int P, const float* means, const float
   fp.flags = per_cam ? (grad_flags & ~(GS_FLAG_XY_PER_CAMERA | (0x1ff << 8))) : grad_flags;
   fp.act = param_flags; fp.sh_rest = sh_rest;
   const FusedOut out = {v_means, v_scales, v_quats, v_opacities, v_sh, v_sh_rest, v_viewmats,
-                        per_cam ? nullptr : v_xy_sum, nullptr, nullptr};
+                        per_cam ? nullptr : v_xy_sum, nullptr, nullptr, dirty, 0};
   const int rc = launch_fused_bwd(fp, sh_degree, records, v_records, out, touched, pose_scratch, pose_scratch_bytes_,
-                                  (hipStream_t)stream);
+                                  (hipStream_t)stream, dirty ? (per_cam ? 2 : 1) : 0);
   if (rc != GS_OK || !per_cam) return rc;
   hipLaunchKernelGGL(xy_grad_cams_kernel, dim3((N + 255) / 256), dim3(256), 0, (hipStream_t)stream, N, P, cams, v_records,
-                     touched, v_xy_sum);
+                     const_cast<unsigned char*>(touched), v_xy_sum, dirty ? 1 : 0);
   return gs_launch_status();
+}
+
+GS_EXPORT int gs_project_fused_bwd(int N, int P, const float* means, const float* scales, float glob_scale,
+                                   const float* quats, const float* opacities, const float* sh, int K_stride,
+                                   int sh_degree, const float* viewmats, float fx, float fy, float cx, float cy,
+                                   int H, int W, float clip, int antialiased, const float* records,
+                                   const float* v_records, float* v_means, float* v_scales, float* v_quats,
+                                   float* v_opacities, float* v_sh, float* v_viewmats,
+                                   const unsigned char* touched, float* v_xy_sum, int grad_flags, const float* sh_rest,
+                                   int param_flags, float* v_sh_rest, void* pose_scratch, long long pose_scratch_bytes_,
+                                   void* stream) {
+  return project_fused_bwd_impl(N, P, means, scales, glob_scale, quats, opacities, sh, K_stride, sh_degree, viewmats, fx,
+                                fy, cx, cy, H, W, clip, antialiased, records, v_records, v_means, v_scales, v_quats,
+                                v_opacities, v_sh, v_viewmats, touched, v_xy_sum, grad_flags, sh_rest, param_flags,
+                                v_sh_rest, pose_scratch, pose_scratch_bytes_, stream, nullptr);
+}
+
+// gs_project_fused_bwd on POOLED gradient buffers: the five (six) gradient arrays are +0.0 everywhere except in the rows
+// flagged in dirty[N] (what an earlier call on the same buffers left behind; a fresh set of buffers: uninitialised
+// arrays and dirty = all ones).  The kernel zeroes just those rows, writes this call's rows and leaves in `dirty` the
+// map of them; `touched` (the caller's persistent flag buffer, all zero before the frame backward set this frame's
+// flags) is all zero again when the call's last launch has run.  No fill launch of 236 MB (1M Gaussians, degree 3) for
+// a frame that reaches half a percent of them.  v_viewmats [P*16] is STORED here (uninitialised rows allowed; every
+// float written, with the bits the accumulating form leaves in zeroed rows); v_xy_sum as in gs_project_fused_bwd with
+// grad flag 32, which this entry point implies.  Results are bit for bit those of gs_project_fused_bwd.
+GS_EXPORT int gs_project_fused_bwd_pooled(int N, int P, const float* means, const float* scales, float glob_scale,
+                                          const float* quats, const float* opacities, const float* sh, int K_stride,
+                                          int sh_degree, const float* viewmats, float fx, float fy, float cx, float cy,
+                                          int H, int W, float clip, int antialiased, const float* records,
+                                          const float* v_records, float* v_means, float* v_scales, float* v_quats,
+                                          float* v_opacities, float* v_sh, float* v_viewmats, unsigned char* touched,
+                                          float* v_xy_sum, int grad_flags, const float* sh_rest, int param_flags,
+                                          float* v_sh_rest, void* pose_scratch, long long pose_scratch_bytes_,
+                                          void* stream, unsigned char* dirty) {
+  if (!touched || !dirty) return GS_ERR_INVALID;
+  return project_fused_bwd_impl(N, P, means, scales, glob_scale, quats, opacities, sh, K_stride, sh_degree, viewmats, fx,
+                                fy, cx, cy, H, W, clip, antialiased, records, v_records, v_means, v_scales, v_quats,
+                                v_opacities, v_sh, v_viewmats, touched, v_xy_sum, grad_flags | GS_FLAG_ZERO_FILL, sh_rest,
+                                param_flags, v_sh_rest, pose_scratch, pose_scratch_bytes_, stream, dirty);
 }
 
 // ---- pixel-velocity model (the paper's first-order blur / rolling-shutter model; SURVEY App. A, C1;

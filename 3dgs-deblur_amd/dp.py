@@ -129,6 +129,13 @@ class _RowOps:
             self._stream = ctypes.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
             self._vp = ctypes.c_void_p
 
+    def _raw_write(self) -> None:
+        """the kernels below write other ranks' rows into the gradients through raw pointers (no version bump): a
+        gradient buffer that ops' gradient pool owns is no longer `zero except its dirty rows` and must not be recycled"""
+        from . import ops
+        for g in self.grads:
+            ops.grad_pool_invalidate(g)
+
     def row_mask(self) -> torch.Tensor:
         if self.hip:
             mask = torch.empty(self.N, dtype=torch.uint8, device=self.dev)
@@ -184,6 +191,7 @@ class _RowOps:
         """grads[row] += scale * row for the rows of a pack_masked payload (count read from its header)"""
         if self.hip:
             payload = payload.contiguous()
+            self._raw_write()
             self._check(self._L.gs_dp_scatter_add_payload(cap, self._vp(payload.data_ptr()), len(self.grads), self._ptrs,
                                                           self._w, float(scale), self._stream), "dp_scatter_add_payload")
             return
@@ -195,6 +203,7 @@ class _RowOps:
         if M == 0:
             return
         if self.hip:
+            self._raw_write()
             self._check(self._L.gs_dp_scatter_add_rows(M, self._vp(payload.data_ptr()), len(self.grads), self._ptrs,
                                                        self._w, float(scale), self._stream), "dp_scatter_add_rows")
             return

@@ -731,9 +731,107 @@ def _arena_return(frame) -> None:
 
 
 def release_arenas() -> None:
-    """drop every pooled frame arena (they return to torch's caching allocator)"""
+    """drop every pooled frame arena and every pooled gradient buffer (they return to torch's caching allocator)"""
     with _state_lock:
         _arena_pool.clear()
+        _grad_pool.clear()
+
+
+# Gradient buffers are POOLED too.  A frame that reaches half a percent of the Gaussians used to store 236 MB of zeros
+# per step (1M Gaussians, degree 3) over memory that already held zeros in all but the rows the previous step wrote.
+# A pool entry keeps the flat gradient buffer of a step together with `dirty` [N] u8 — the map of the rows that step
+# wrote, kept by the projection backward itself (gs_project_fused_bwd_pooled) — and a persistent `touched` [P*N] flag
+# buffer the same call hands back all zero.  The next step of the same shape zeroes just the dirty rows.
+# OWNERSHIP RULE: the buffer is zero outside its dirty rows only as long as nobody but the library's own launch wrote to
+# it, so an entry is recycled only if
+#   * nothing outside the pool can still reach its storage (storage use count: a view or a .grad still alive blocks it),
+#   * its version counter is what it was when it was handed out (an in-place torch op of the caller's — gradient
+#     clipping, grad.mul_() — bumps it),
+#   * none of the project's raw-pointer writers wrote to it (dp.py's exchange calls grad_pool_invalidate), and
+#   * the launch that produced it returned success (an entry is invalid from acquire until that moment).
+# Otherwise the step gets a FRESH entry — uninitialised buffer, dirty all ones: every block of the kernel streams zeros
+# over its whole chunk, which is the full fill of before.  Both routes give bitwise the same gradients.
+# One pool per (device, stream), at most two entries each (two steps' gradients alive at once); an entry also carries
+# its shape key (N, P, K, sh_rest split) and only serves steps of that shape.
+GRAD_POOL = True        # False: every step allocates its buffers and fills them in full (tests compare the two routes)
+_grad_pool = {}         # (device, stream) -> [_GradEntry]; guarded by _state_lock
+_GRAD_POOL_KEEP = 2
+
+
+def _storage_use_count(t: Tensor) -> int:
+    """references to t's storage (tensors that share it + the temporary wrapper this call makes)"""
+    fn = getattr(torch._C, "_storage_Use_Count", None)
+    if fn is None:
+        return 1 << 30          # cannot tell: nothing is ever recycled
+    return int(fn(t.untyped_storage()._cdata))
+
+
+_STORAGE_FREE = _storage_use_count(torch.empty(1))      # the count of a storage only ONE tensor holds
+
+
+class _GradEntry:
+    __slots__ = ("pool_key", "shape_key", "flat", "dirty", "touched", "version", "valid")
+
+    def __init__(self, pool_key, shape_key, flat, dirty, touched):
+        self.pool_key, self.shape_key = pool_key, shape_key
+        self.flat, self.dirty, self.touched = flat, dirty, touched
+        self.version, self.valid = flat._version, False
+
+    def recyclable(self) -> bool:
+        return (self.valid and self.flat._version == self.version
+                and _storage_use_count(self.flat) <= _STORAGE_FREE)
+
+
+def _grad_pool_acquire(dev, N: int, P: int, K: int, split: bool, alloc=None) -> _GradEntry:
+    """an entry for one projection backward: a recycled one if the ownership rule holds for it, else a fresh one.  The
+    entry leaves the pool (valid = False) until _grad_pool_commit hands it back after a successful launch.
+    alloc (tests): (flat floats, N, P) -> (flat, dirty, touched) in place of the device allocations."""
+    stream = torch.cuda.current_stream(dev).cuda_stream if torch.device(dev).type == "cuda" else 0
+    pool_key, shape_key = (str(dev), stream), (int(N), int(P), int(K), bool(split))
+    with _state_lock:
+        entries = _grad_pool.setdefault(pool_key, [])
+        # whatever broke the rule for an entry (or changed shape) stays broken: such entries are dropped here
+        hit = None
+        for e in list(entries):
+            if e.shape_key == shape_key and e.recyclable():
+                hit = hit or e
+            elif not e.valid or e.flat._version != e.version or e.shape_key != shape_key:
+                entries.remove(e)
+        if hit is not None:
+            entries.remove(hit)
+            hit.valid = False
+            return hit
+    n_flat = (3 + 3 + 4 + 1 + 3 * K) * N
+    if alloc is not None:
+        flat, dirty, touched = alloc(n_flat, N, P)
+    else:
+        flat = torch.empty(n_flat, device=dev)
+        dirty = torch.ones(N, dtype=torch.uint8, device=dev)
+        touched = torch.zeros(P * N, dtype=torch.uint8, device=dev)
+    return _GradEntry(pool_key, shape_key, flat, dirty, touched)
+
+
+def _grad_pool_commit(entry: _GradEntry) -> None:
+    """the launch that wrote `entry` returned success: it may serve a later step (once its tensors are dropped)"""
+    with _state_lock:
+        entry.version, entry.valid = entry.flat._version, True
+        entries = _grad_pool.setdefault(entry.pool_key, [])
+        if entry not in entries:
+            entries.append(entry)
+        while len(entries) > _GRAD_POOL_KEEP:
+            entries.pop(0)
+
+
+def grad_pool_invalidate(t: Tensor) -> None:
+    """a raw-pointer writer of the project's (dp.py's exchange kernels) is about to write to `t`: if a pool entry owns
+    that storage its rows are no longer `zero except the dirty ones` and it is never recycled"""
+    ptr = t.untyped_storage().data_ptr()
+    with _state_lock:
+        for entries in _grad_pool.values():
+            for e in list(entries):
+                if e.flat.untyped_storage().data_ptr() == ptr:
+                    e.valid = False
+                    entries.remove(e)
 
 
 _pinned_cache = {}
@@ -1158,11 +1256,11 @@ class _SubposeViewmats(Function):
         V, lin, ang, times = ctx.saved_tensors
         P = times.numel()
         dev = V.device
-        acc = torch.zeros(22, device=dev)                  # one fill for the three accumulators
+        acc = torch.empty(22, device=dev)                  # the one-block kernel stores all 22 floats: no fill launch
         v_V, v_lin, v_ang = acc[:16].view(4, 4), acc[16:19], acc[19:22]
-        _check(_L().gs_subpose_viewmats_bwd(P, _ptr(V), _ptr(lin), _ptr(ang), _ptr(times),
-                                            _ptr(v_out.contiguous().float()), _ptr(v_V), _ptr(v_lin), _ptr(v_ang),
-                                            _stream()), "subpose_viewmats_bwd")
+        _check(_L().gs_subpose_viewmats_bwd_store(P, _ptr(V), _ptr(lin), _ptr(ang), _ptr(times),
+                                                  _ptr(v_out.contiguous().float()), _ptr(v_V), _ptr(v_lin), _ptr(v_ang),
+                                                  _stream()), "subpose_viewmats_bwd_store")
         return v_V, v_lin, v_ang, None
 
 
@@ -1345,7 +1443,15 @@ class _RenderSubposes(Function):
                 raise ValueError("exact rolling shutter renders with rs_bands == 1")
             # the backward's frame-sized buffers (and the one fill among them) are issued BEFORE the frame: behind the
             # frame's last read-back nothing but the averaging and the backward's own launches are left for the host
-            if any(ctx.needs_input_grad):
+            if any(ctx.needs_input_grad) and GRAD_POOL and not pixvel:
+                # pooled gradient buffers (see _grad_pool): the entry is taken here, ahead of the frame like every other
+                # buffer of the backward; its persistent touched flags are all zero, and the projection backward stores
+                # the view-matrix gradients — no fill at all.  An entry whose backward never runs is never committed.
+                entry = _grad_pool_acquire(dev, N, P, K, sh_rest is not None)
+                ctx.prealloc = {"entry": entry, "touched": entry.touched,
+                                "v_records": torch.empty(P * N, GRAD, device=dev),
+                                "pose_scratch": _pose_scratch(N, P, True, dev)}
+            elif any(ctx.needs_input_grad):
                 # ONE zero fill for what this node's backward accumulates into: touched flags [P*N] u8 | 16 P + 12 floats
                 # of view-matrix / twist gradients
                 t_len = (P * N + 15) // 16 * 16
@@ -1466,7 +1572,11 @@ class _RenderSubposes(Function):
         all_tuples = ctx.frame is not None or all(sl["gi_of_e"] is not None for sl in ctx.slices)
         pre = ctx.prealloc if ctx.prealloc else {}
         ctx.prealloc = None
-        if all_tuples and "touched" in pre:
+        entry = None
+        if all_tuples and pre.get("entry") is not None and ctx.frame is not None:
+            entry = pre["entry"]
+            v_records, touched = pre["v_records"], entry.touched
+        elif all_tuples and "touched" in pre:
             v_records, touched = pre["v_records"], pre["touched"]
         elif all_tuples:
             v_records = torch.empty(P * N, GRAD, device=dev)
@@ -1490,7 +1600,7 @@ class _RenderSubposes(Function):
         sh_rest = ctx.sh_rest
         sizes = [3 * N, 3 * N, 4 * N, N] + ([3 * K * N] if sh_rest is None else [3 * N, 3 * (K - 1) * N])
         shapes = [(N, 3), (N, 3), (N, 4), (N,)] + ([(N, K, 3)] if sh_rest is None else [tuple(sh.shape), (N, K - 1, 3)])
-        flat = torch.empty(sum(sizes), device=dev)
+        flat = torch.empty(sum(sizes), device=dev) if entry is None else entry.flat
         outs = [t.view(shape) for t, shape in zip(flat.split(sizes), shapes)]
         v_means, v_scales, v_quats, v_opac, v_sh = outs[:5]
         v_sh_rest = outs[5] if sh_rest is not None else None
@@ -1522,6 +1632,17 @@ class _RenderSubposes(Function):
                        "project_pixvel_bwd")
                 if v_tw is not None:
                     v_lin, v_ang = v_tw[0:3], v_tw[3:6]
+            elif entry is not None:
+                # pooled: only the rows the entry's last step dirtied are zeroed; v_V is stored, not accumulated into
+                v_V = torch.empty(P, 4, 4, device=dev) if need_v else None
+                _check(L.gs_project_fused_bwd_pooled(N, P, _ptr(means3d), _ptr(scales), glob, _ptr(quats),
+                                                     _ptr(opacities), _ptr(sh), K, deg, _ptr(V), fx, fy, cx, cy, H, W,
+                                                     clip, aa, _ptr(records), _ptr(v_records), _ptr(v_means),
+                                                     _ptr(v_scales), _ptr(v_quats), _ptr(v_opac), _ptr(v_sh), _ptr(v_V),
+                                                     _ptr(touched), _ptr(xy_out), _proj_grad_flags() | fill_flag | xy_cams,
+                                                     _ptr(sh_rest), pf, _ptr(v_sh_rest), _ptr(psc), psc_n, _stream(),
+                                                     _ptr(entry.dirty)), "project_fused_bwd_pooled")
+                _grad_pool_commit(entry)
             else:
                 v_V = (pre["v_V"].view(P, 4, 4) if "v_V" in pre else torch.zeros(P, 4, 4, device=dev)) if need_v else None
                 _check(L.gs_project_fused_bwd(N, P, _ptr(means3d), _ptr(scales), glob, _ptr(quats), _ptr(opacities),

@@ -64,6 +64,11 @@ int gs_subpose_viewmats_fwd(int P, const float* viewmat /*16*/, const float* lin
 int gs_subpose_viewmats_bwd(int P, const float* viewmat, const float* lin_vel, const float* ang_vel,
                             const float* times, const float* v_out /*P*16*/, float* v_viewmat,
                             float* v_lin, float* v_ang, void* stream);
+/* the same sums STORED: v_viewmat[16] (row 3 = 0), v_lin[3], v_ang[3] may be uninitialised; every float is written, with
+ * the bits gs_subpose_viewmats_bwd leaves in zeroed buffers (no fill launch in front of a one-block kernel) */
+int gs_subpose_viewmats_bwd_store(int P, const float* viewmat, const float* lin_vel, const float* ang_vel,
+                                  const float* times, const float* v_out /*P*16*/, float* v_viewmat,
+                                  float* v_lin, float* v_ang, void* stream);
 
 /* ---- gsplat.project_gaussians (upstream _C.project_gaussians_forward/backward; SURVEY §8 a1,a3)
  * needed by: train.py:40 (camera-optimizer => viewmat grads), train.py:119 (antialiased => comp). */
@@ -164,6 +169,23 @@ int gs_project_fused_bwd(int N, int P, const float* means3d, const float* scales
                                        atomics whose order changed from run to run); NULL otherwise*/,
                          long long pose_scratch_bytes,
                          void* stream);
+/* gs_project_fused_bwd on POOLED gradient buffers (grad flag 32 implied; bit-identical results).  The five (six)
+ * gradient arrays are +0.0 everywhere except in the rows flagged in dirty[N] — what an earlier call on the same buffers
+ * left behind (a fresh set: uninitialised arrays, dirty = all ones).  A block of the sparse kernel zeroes the dirty rows
+ * of its 2048 Gaussians (more than a quarter of them dirty: it streams zeros over the whole chunk), writes this call's
+ * rows and stores in `dirty` the map of them.  `touched`: the caller's persistent flag buffer — all zero before the frame
+ * backward set this frame's flags, all zero again after this call (its last launch that reads the flags clears the ones
+ * it found set).  v_viewmats [P*16] is STORED (uninitialised rows allowed, every float written).  The caller owns the
+ * invariant: nothing else may have written to the arrays since the call that produced `dirty`. */
+int gs_project_fused_bwd_pooled(int N, int P, const float* means3d, const float* scales, float glob_scale,
+                                const float* quats, const float* opacities, const float* sh, int K_stride,
+                                int sh_degree, const float* viewmats, float fx, float fy, float cx, float cy,
+                                int img_height, int img_width, float clip_thresh, int antialiased,
+                                const float* records, const float* v_records, float* v_means3d, float* v_scales,
+                                float* v_quats, float* v_opacities, float* v_sh, float* v_viewmats,
+                                unsigned char* touched, float* v_xy_sum, int grad_flags, const float* sh_rest,
+                                int param_flags, float* v_sh_rest, void* pose_scratch, long long pose_scratch_bytes,
+                                void* stream, unsigned char* dirty /*[N]*/);
 
 /* ---- pixel-velocity model: the paper's first-order blur / rolling-shutter model (the fork's
  * own wording at /root/reference/README.md:200 "Fixed a bug in pixel velocity formulas").  ONE projection under the
