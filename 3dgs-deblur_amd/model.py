@@ -638,3 +638,10 @@ class SplatfactoDeblurModel(nn.Module):
         m = SplatfactoDeblurModel(config, scene["means"], scene["log_scales"], scene["quats"],
                                   scene["opacity_logits"], sh[:, 0, :], sh[:, 1:, :], num_cameras)
         return m.to(device)
+
+    @staticmethod
+    def from_ply(path, config: Optional[SplatfactoDeblurConfig] = None, device="cpu", num_cameras: int = 1):
+        """Build from a Gaussian-splat PLY (checkpoint.export_ply / the 3DGS viewers' format): config None = the
+        defaults at the file's SH degree.  Camera-side parameters and bilateral grids are not in a PLY."""
+        from .checkpoint import model_from_ply
+        return model_from_ply(path, config, device, num_cameras)

@@ -490,7 +490,8 @@ def evaluate(model: SplatfactoDeblurModel, cameras, images, indices, batch_size:
 def train_scene(model: SplatfactoDeblurModel, scene, images, iterations: int, lr_scale: float = 1.0,
                 ssim_lambda: float = 0.2, optimize_eval_cameras: bool = False, eval_camera_every: int = 4,
                 densify=None, log_every: int = 0, seed: int = 0, depths=None, depth_lambda: float = 0.0,
-                batch_size: int = 1, optimizer: Optional[str] = None) -> Dict:
+                batch_size: int = 1, optimizer: Optional[str] = None, checkpoint_path=None, checkpoint_every: int = 0,
+                resume=None) -> Dict:
     """Train on scene.train_indices (one view per step, seeded shuffle), optionally refining the evaluation cameras
     in between; returns {'results': {psnr, ssim}, 'wall_clock_time_seconds', 'history'} like the reference's
     metrics.json (/root/reference/train.py:87-100, parse_outputs.py:58).  depths (optional): per-frame depth maps
@@ -499,11 +500,31 @@ def train_scene(model: SplatfactoDeblurModel, scene, images, iterations: int, lr
     (train_step with lists), and the evaluation renders in batches of that size.  optimizer: make_optimizers' choice
     ("adam" / "selective_adam"; default model.config.optimizer).  densify: a densify.DensifyConfig (splatfacto's split /
     duplicate / cull schedule, driven by the screen-space gradient statistic) or an mcmc.MCMCConfig (fixed-budget
-    relocation + per-step noise; no statistic is collected, collect_densify_stats stays off)."""
+    relocation + per-step noise; no statistic is collected, collect_densify_stats stays off).
+    checkpoint_path: checkpoint.save_checkpoint writes model, optimizers, loop state and densification accumulators there
+    after the last step, and with checkpoint_every=K also after steps K, 2K, ...  resume=path: restore all of that into
+    `model` (same config; its Gaussian parameters are replaced by the saved ones, whatever their row count) and continue
+    at the saved iteration + 1 with the saved optimizers (`lr_scale`, `optimizer` and `seed` are then the file's);
+    `iterations` stays the total target, and the returned wall_clock_time_seconds and history continue the saved ones.
+    Under an initialised process group only rank 0 writes, then all ranks barrier."""
     import time
     from . import mcmc as M
     use_mcmc = isinstance(densify, M.MCMCConfig)
-    optimizers = make_optimizers(model, lr_scale, optimizer=optimizer)
+    if checkpoint_every and checkpoint_path is None:
+        raise ValueError("checkpoint_every needs checkpoint_path")
+    loaded = None
+    if resume is not None:
+        from . import checkpoint as C
+        loaded = C.load_checkpoint(resume, into=model)
+        if loaded.optimizers is None or loaded.trainer is None:
+            raise ValueError(f"{resume}: a checkpoint without optimizer / trainer state cannot be resumed")
+        strategy = None if densify is None else ("mcmc" if use_mcmc else "splatfacto")
+        if loaded.trainer.get("strategy") != strategy:
+            raise ValueError(f"{resume} was trained with densify strategy {loaded.trainer.get('strategy')!r}, "
+                             f"this call asks for {strategy!r}")
+        optimizers = loaded.optimizers
+    else:
+        optimizers = make_optimizers(model, lr_scale, optimizer=optimizer)
     g = torch.Generator().manual_seed(seed)
     order = []
     history = []
@@ -521,7 +542,31 @@ def train_scene(model: SplatfactoDeblurModel, scene, images, iterations: int, lr
             import dataclasses
             densify = dataclasses.replace(densify, num_train_data=len(scene.train_indices))
     ev_pos = 0
-    for it in range(1, iterations + 1):
+    first, wall0 = 1, 0.0
+    if loaded is not None:
+        tr = loaded.trainer
+        first, seed, ev_pos = int(tr["iteration"]) + 1, int(tr["seed"]), int(tr["ev_pos"])
+        g.set_state(tr["generator_state"])
+        order, history = [int(i) for i in tr["order"]], list(tr["history"])
+        wall0, lr_scale = float(tr["wall_clock_time_seconds"]), float(tr["lr_scale"])
+        if state is not None and loaded.densify_state is not None:
+            state = loaded.densify_state
+        C.restore_default_generators(tr, model.means.device)
+
+    def save(it):
+        import torch.distributed as dist
+        from . import checkpoint as C
+        if model.means.is_cuda:
+            torch.cuda.synchronize()
+        multi = dist.is_available() and dist.is_initialized()
+        if not multi or dist.get_rank() == 0:
+            C.save_checkpoint(checkpoint_path, model, optimizers, densify_state=state,
+                              trainer=C.trainer_state(it, seed, g, order, ev_pos, history, wall0 + time.time() - t0,
+                                                      lr_scale, ssim_lambda, densify, model.means.device))
+        if multi:
+            dist.barrier()
+
+    for it in range(first, iterations + 1):
         if not order:
             order = [scene.train_indices[j] for j in torch.randperm(len(scene.train_indices), generator=g).tolist()]
         if batch_size > 1:
@@ -545,8 +590,10 @@ def train_scene(model: SplatfactoDeblurModel, scene, images, iterations: int, lr
             eval_camera_step(model, optimizers, scene.cameras[e], images[e], ssim_lambda)
         if log_every and it % log_every == 0:
             history.append({"step": it, **h})
+        if checkpoint_path is not None and (it == iterations or (checkpoint_every and it % checkpoint_every == 0)):
+            save(it)
     if model.means.is_cuda:
         torch.cuda.synchronize()
-    wall = time.time() - t0
+    wall = wall0 + time.time() - t0
     res = evaluate(model, scene.cameras, images, scene.eval_indices, batch_size=batch_size)
     return {"results": res, "wall_clock_time_seconds": wall, "history": history}

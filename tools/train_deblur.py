@@ -9,7 +9,9 @@ Variants follow /root/reference/train.py:29-76: blur_samples 0 = no motion-blur 
 5 (the default, train.py:46) and 10 (synthetic sets, train.py:22); --motion-model picks the SE(3) re-projection
 (north_star) or the paper's pixel-velocity model; --optimize-eval-cameras refines the evaluation poses without
 touching the Gaussians (train.py:180-183); --densify adds splatfacto's refinement schedule or 3DGS-MCMC (--cap-max);
---bilateral-grid learns a per-image colour correction with the scene."""
+--bilateral-grid learns a per-image colour correction with the scene.  Every variant leaves checkpoint_<name>.pt beside
+its metrics_<name>.json (--checkpoint-every K: also every K steps; --resume PATH continues from one; --export-ply adds
+splat_<name>.ply for a viewer); tools/render_model.py renders either file."""
 import argparse
 import json
 import os
@@ -52,8 +54,16 @@ def main():
     ap.add_argument("--bilateral-grid", action="store_true",
                     help="per-image bilateral-grid colour correction of the training renders (exposure / white-balance "
                          "drift); evaluation renders are never corrected")
+    ap.add_argument("--checkpoint-every", type=int, default=0,
+                    help="also write checkpoint_<name>.pt every K steps (it is always written after the last step)")
+    ap.add_argument("--resume", default=None,
+                    help="continue from a checkpoint: a file (one --blur-samples value), or a directory holding "
+                         "checkpoint_<name>.pt for every variant of the run; --iterations stays the total")
+    ap.add_argument("--export-ply", action="store_true", help="write splat_<name>.ply (Gaussian-splat PLY) per variant")
     ap.add_argument("--out", default="gpurun_out/deblur")
     args = ap.parse_args()
+    if args.resume and not os.path.isdir(args.resume) and len(args.blur_samples) != 1:
+        ap.error("--resume FILE continues one variant: give one --blur-samples value, or a directory")
     dev = torch.device("cuda", 0)
     root = args.data
     if args.generate:
@@ -89,11 +99,17 @@ def main():
         if args.optimize_eval_cameras:
             cfg.camera_optimizer.mode = "SO3xR3"
         model = SD.init_from_seed_points(cfg, xyz, rgb, dev, num_cameras=len(scene.cameras))
-        res = gs.training.train_scene(model, scene, images, args.iterations,
-                                      optimize_eval_cameras=args.optimize_eval_cameras, log_every=100,
-                                      densify=dcfg)
         name = (f"blur_samples_{bs}" + ("_pixvel" if args.motion_model == "pixel_velocity" else "") +
                 ("" if args.rolling_shutter_time <= 0 else f"_rs_{args.rolling_shutter_mode}"))
+        resume = args.resume
+        if resume and os.path.isdir(resume):
+            resume = os.path.join(resume, f"checkpoint_{name}.pt")
+        res = gs.training.train_scene(model, scene, images, args.iterations,
+                                      optimize_eval_cameras=args.optimize_eval_cameras, log_every=100,
+                                      densify=dcfg, checkpoint_path=os.path.join(args.out, f"checkpoint_{name}.pt"),
+                                      checkpoint_every=args.checkpoint_every, resume=resume)
+        if args.export_ply:
+            gs.checkpoint.export_ply(os.path.join(args.out, f"splat_{name}.ply"), model)
         with open(os.path.join(args.out, f"metrics_{name}.json"), "wt") as f:
             json.dump({"results": res["results"], "wall_clock_time_seconds": res["wall_clock_time_seconds"]}, f)
         table[name] = res["results"] | {"time": round(res["wall_clock_time_seconds"], 1)}
