@@ -19,11 +19,12 @@ from .ops import (  # noqa: F401
     render_batch,
     subpose_viewmats,
     subpose_schedule,
+    subpose_times,
     combine_samples,
     exclusive_scan_u32,
     radix_sort_pairs,
 )
-from .model import Camera, SplatfactoDeblurConfig, SplatfactoDeblurModel  # noqa: F401
+from .model import Camera, CameraShutterOptimizerConfig, SplatfactoDeblurConfig, SplatfactoDeblurModel  # noqa: F401
 from . import dp  # noqa: F401
 from . import bilagrid, checkpoint, data, densify, fused, mcmc, step, train_step as training  # noqa: F401
 from .step import render_step  # noqa: F401

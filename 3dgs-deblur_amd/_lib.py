@@ -16,6 +16,7 @@ _SIGS = {
     "gs_subpose_viewmats_fwd": [_I, _P, _P, _P, _P, _P, _P],
     "gs_subpose_viewmats_bwd": [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "gs_subpose_viewmats_bwd_store": [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "gs_subpose_viewmats_bwd_times": [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "gs_project_fwd": [_I, _P, _P, _F, _P, _P, _F, _F, _F, _F, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "gs_project_bwd": [_I, _P, _P, _F, _P, _P, _F, _F, _F, _F, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _L, _P],
     "gs_sh_fwd": [_I, _I, _I, _P, _P, _P, _P],

@@ -10,7 +10,8 @@ is no fallback to full unpickling.  Layout (version 1):
 
     format "gsdeblur-checkpoint", version 1
     model       config (dataclasses.asdict of SplatfactoDeblurConfig), num_cameras, step, params {the six gauss_params},
-                background_param / pose_adjustment / velocity_adjustment / bilateral_grids (tensor or None)
+                background_param / pose_adjustment / velocity_adjustment / bilateral_grids (tensor or None);
+                exposure_adjustment / readout_adjustment (tensor) ONLY when the shutter optimizer has them
     optimizers  None, or {"kind": "adam" | "selective_adam", "groups": {name: lr, betas, eps, step, exp_avg, exp_avg_sq}}
     trainer     None, or train_scene's loop state (trainer_state)
     densify_state  None, or DensifyState's accumulators
@@ -41,13 +42,17 @@ from typing import Any, Dict, List, Optional
 import torch
 from torch import Tensor
 
-from .model import CameraOptimizerConfig, CameraVelocityOptimizerConfig, SplatfactoDeblurConfig, SplatfactoDeblurModel
+from .model import (CameraOptimizerConfig, CameraShutterOptimizerConfig, CameraVelocityOptimizerConfig,
+                    SplatfactoDeblurConfig, SplatfactoDeblurModel)
 
 FORMAT = "gsdeblur-checkpoint"
 VERSION = 1
 
 GAUSS_NAMES = ("means", "scales", "quats", "opacities", "features_dc", "features_rest")
 SMALL_NAMES = ("background_param", "pose_adjustment", "velocity_adjustment", "bilateral_grids")
+# the shutter optimizer's parameters: their keys are written ONLY when the parameter exists (a file of a model without
+# them has exactly the keys it always had), and a file without the keys loads as "off"
+SHUTTER_NAMES = ("exposure_adjustment", "readout_adjustment")
 
 
 # --------------------------------------------------------------------------- #
@@ -106,7 +111,8 @@ def config_to_dict(config: SplatfactoDeblurConfig) -> Dict:
     return d
 
 
-_NESTED = {"camera_optimizer": CameraOptimizerConfig, "camera_velocity_optimizer": CameraVelocityOptimizerConfig}
+_NESTED = {"camera_optimizer": CameraOptimizerConfig, "camera_velocity_optimizer": CameraVelocityOptimizerConfig,
+           "camera_shutter_optimizer": CameraShutterOptimizerConfig}
 
 
 def _dataclass_from_dict(cls, d: Dict, where: str):
@@ -137,6 +143,10 @@ def _model_section(model: SplatfactoDeblurModel) -> Dict:
     for k in SMALL_NAMES:
         p = getattr(model, k, None)
         sec[k] = None if p is None else p.data
+    for k in SHUTTER_NAMES:
+        p = getattr(model, k, None)
+        if p is not None:
+            sec[k] = p.data
     return sec
 
 
@@ -149,16 +159,25 @@ def optimizer_kind(optimizers: Dict[str, torch.optim.Optimizer]) -> str:
 def _optimizers_section(optimizers: Dict[str, torch.optim.Optimizer]) -> Dict:
     groups = {}
     for name, opt in optimizers.items():
-        if len(opt.param_groups) != 1 or len(opt.param_groups[0]["params"]) != 1:
-            raise ValueError(f"optimizer {name!r}: one parameter per optimizer expected (make_optimizers' layout)")
+        if len(opt.param_groups) != 1 or len(opt.param_groups[0]["params"]) < 1:
+            raise ValueError(f"optimizer {name!r}: one parameter group expected (make_optimizers' layout)")
         grp = opt.param_groups[0]
-        st = opt.state.get(grp["params"][0], None)
-        rec = {"lr": float(grp["lr"]), "betas": [float(b) for b in grp["betas"]], "eps": float(grp["eps"]),
-               "step": None, "exp_avg": None, "exp_avg_sq": None}
-        if st:
-            # HipAdam: int; torch.optim.Adam / SelectiveAdam: float tensor — the file holds an int
-            rec["step"] = int(st["step"])
-            rec["exp_avg"], rec["exp_avg_sq"] = st["exp_avg"], st["exp_avg_sq"]
+        rec = {"lr": float(grp["lr"]), "betas": [float(b) for b in grp["betas"]], "eps": float(grp["eps"])}
+        states = []
+        for param in grp["params"]:
+            st = opt.state.get(param, None)
+            one = {"step": None, "exp_avg": None, "exp_avg_sq": None}
+            if st:
+                # HipAdam: int; torch.optim.Adam / SelectiveAdam: float tensor — the file holds an int
+                one["step"] = int(st["step"])
+                one["exp_avg"], one["exp_avg_sq"] = st["exp_avg"], st["exp_avg_sq"]
+            states.append(one)
+        if len(states) == 1:
+            rec.update(states[0])
+        else:
+            # a group of several parameters ("camera_shutter_opt"): the three state keys hold lists, in parameter order
+            for key in ("step", "exp_avg", "exp_avg_sq"):
+                rec[key] = [one[key] for one in states]
         groups[name] = rec
     return {"kind": optimizer_kind(optimizers), "groups": groups}
 
@@ -250,7 +269,7 @@ def _build_model(sec: Dict, device) -> SplatfactoDeblurModel:
 
 def _fill_small(model: SplatfactoDeblurModel, sec: Dict) -> None:
     with torch.no_grad():
-        for k in SMALL_NAMES:
+        for k in SMALL_NAMES + SHUTTER_NAMES:
             saved, have = sec.get(k), getattr(model, k, None)
             if (saved is None) != (have is None):
                 raise ValueError(f"checkpoint and config disagree about {k}: "
@@ -294,19 +313,26 @@ def _build_optimizers(model: SplatfactoDeblurModel, sec: Dict) -> Dict[str, torc
         rec = groups[name]
         grp = opt.param_groups[0]
         grp["lr"], grp["betas"], grp["eps"] = float(rec["lr"]), tuple(float(b) for b in rec["betas"]), float(rec["eps"])
-        if rec["step"] is None:
-            continue
-        param = grp["params"][0]
-        st = {}
-        for key in ("exp_avg", "exp_avg_sq"):
-            m = rec[key]
-            if tuple(m.shape) != tuple(param.shape):
-                raise ValueError(f"optimizer {name!r}: {key} has shape {tuple(m.shape)}, its parameter {tuple(param.shape)}")
-            st[key] = m.to(device=param.device, dtype=param.dtype).contiguous().clone()
-        # fused.HipAdam counts in an int, torch.optim.Adam and train_step.SelectiveAdam in a float tensor on the CPU
-        step = int(rec["step"])
-        st["step"] = step if type(opt).__name__ == "HipAdam" else torch.tensor(float(step))
-        opt.state[param] = st
+        params = grp["params"]
+        if len(params) == 1:
+            per_param = [(rec["step"], rec["exp_avg"], rec["exp_avg_sq"])]
+        else:
+            if not all(isinstance(rec[key], list) and len(rec[key]) == len(params) for key in ("step", "exp_avg", "exp_avg_sq")):
+                raise ValueError(f"optimizer {name!r}: the model has {len(params)} parameters in this group, the file's "
+                                 f"state does not")
+            per_param = list(zip(rec["step"], rec["exp_avg"], rec["exp_avg_sq"]))
+        for param, (step, exp_avg, exp_avg_sq) in zip(params, per_param):
+            if step is None:
+                continue
+            st = {}
+            for key, m in (("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq)):
+                if tuple(m.shape) != tuple(param.shape):
+                    raise ValueError(f"optimizer {name!r}: {key} has shape {tuple(m.shape)}, its parameter {tuple(param.shape)}")
+                st[key] = m.to(device=param.device, dtype=param.dtype).contiguous().clone()
+            # fused.HipAdam counts in an int, torch.optim.Adam and train_step.SelectiveAdam in a float tensor on the CPU
+            step = int(step)
+            st["step"] = step if type(opt).__name__ == "HipAdam" else torch.tensor(float(step))
+            opt.state[param] = st
     return opts
 
 

@@ -723,4 +723,42 @@ GS_HD float sqrt(float a) { return sqrtf(a); }
 GS_HD float sin(float a) { return sinf(a); }
 GS_HD float cos(float a) { return cosf(a); }
 
+// ---- one work item of the screw interpolation's VJP ----------------------------
+// Item (sub-pose, tangent t): input t of the 19 — 12 viewmat entries (rows 0..2), 3 lin, 3 ang, and the sub-pose's own
+// TIME (t == 18) — carries a unit dual part through subpose_viewmat<Dual<1>>; the result is the dot product of the
+// sub-pose's output cotangent v_out12 (rows 0..2 of v_out[p]) with d V_p / d input_t.  For t < 18 the time's dual part is
+// zero, exactly what D(time) holds: the 18 camera tangents see the same operands in the same order whether or not the
+// time tangent is computed beside them.  t == 18 is d V_p / d t_p = -xi^ V_p (xi^ = [[ang]x lin; 0 0]), through the
+// SAME chain — at the small angles of a blurred frame that is the series branch of se3_exp, which keeps its digits.
+GS_HD float subpose_tangent_dot(const float* V0 /*12*/, const float* lin /*3*/, const float* ang /*3*/, float time,
+                                const float* v_out12 /*12*/, int t) {
+  typedef Dual<1> D;
+  D dV[12], dl[3], da[3], o[12];
+  for (int j = 0; j < 12; ++j) { dV[j] = D(V0[j]); dV[j].d[0] = (j == t) ? 1.f : 0.f; }
+  for (int j = 0; j < 3; ++j) {
+    dl[j] = D(lin[j]); dl[j].d[0] = (12 + j == t) ? 1.f : 0.f;
+    da[j] = D(ang[j]); da[j].d[0] = (15 + j == t) ? 1.f : 0.f;
+  }
+  D dt(time);
+  dt.d[0] = (t == 18) ? 1.f : 0.f;
+  subpose_viewmat<D>(dV, dl, da, dt, o);
+  float acc = 0.f;
+  for (int j = 0; j < 12; ++j) acc += v_out12[j] * o[j].d[0];
+  return acc;
+}
+
+// the closed form of the time tangent, -<v_out_p, xi^ V_p> with V_p the sub-pose's viewmat rows 0..2: the check of
+// subpose_tangent_dot(..., 18) (tests; the kernels use the dual chain)
+GS_HD float subpose_time_dot_closed(const float* Vp /*12*/, const float* lin, const float* ang, const float* v_out12) {
+  float acc = 0.f;
+  const float K[9] = {0.f, -ang[2], ang[1], ang[2], 0.f, -ang[0], -ang[1], ang[0], 0.f};
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 4; ++j) {
+      float x = K[i * 3 + 0] * Vp[0 * 4 + j] + K[i * 3 + 1] * Vp[1 * 4 + j] + K[i * 3 + 2] * Vp[2 * 4 + j];
+      if (j == 3) x = x + lin[i];
+      acc += v_out12[i * 4 + j] * x;
+    }
+  return -acc;
+}
+
 }  // namespace gs

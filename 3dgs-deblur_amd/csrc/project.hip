@@ -35,24 +35,22 @@ __global__ void subpose_fwd_kernel(int P, const float* __restrict__ V0, const fl
 // ONE block (round 6): the P contributions to every tangent are parked in LDS and added up in sub-pose order by one
 // thread per tangent — the camera-level gradients are what the pose / velocity optimizers consume
 // (/root/reference/train.py:40,66), and fp32 atomics across sub-poses made them differ from run to run.
+template <bool TIMES>
 __global__ __launch_bounds__(256) void subpose_bwd_kernel(int P, const float* __restrict__ V0, const float* __restrict__ lin,
                                    const float* __restrict__ ang, const float* __restrict__ times,
                                    const float* __restrict__ v_out, float* __restrict__ v_V0,
-                                   float* __restrict__ v_lin, float* __restrict__ v_ang, int store) {
-  typedef Dual<1> D;
+                                   float* __restrict__ v_lin, float* __restrict__ v_ang, float* __restrict__ v_times,
+                                   int store) {
+  // TIMES: a 19th item per sub-pose, the tangent of the sub-pose's own time (gs_math.h::subpose_tangent_dot, t == 18).
+  // It has ONE writer per v_times[p] and no sum over p, so it goes straight to memory: LDS stays [P][18], and the 18
+  // camera tangents go through the same arithmetic and the same ordered sums as without it.
+  constexpr int NT = TIMES ? 19 : 18;
   extern __shared__ float sp_part[];          // [P][18]
-  for (int gid = threadIdx.x; gid < P * 18; gid += blockDim.x) {
-    const int p = gid / 18, t = gid - p * 18;
-    D dV[12], dl[3], da[3], o[12];
-    for (int j = 0; j < 12; ++j) { dV[j] = D(V0[j]); dV[j].d[0] = (j == t) ? 1.f : 0.f; }
-    for (int j = 0; j < 3; ++j) {
-      dl[j] = D(lin[j]); dl[j].d[0] = (12 + j == t) ? 1.f : 0.f;
-      da[j] = D(ang[j]); da[j].d[0] = (15 + j == t) ? 1.f : 0.f;
-    }
-    subpose_viewmat<D>(dV, dl, da, D(times[p]), o);
-    float acc = 0.f;
-    for (int j = 0; j < 12; ++j) acc += v_out[16 * p + j] * o[j].d[0];
-    sp_part[gid] = acc;
+  for (int gid = threadIdx.x; gid < P * NT; gid += blockDim.x) {
+    const int p = gid / NT, t = gid - p * NT;
+    const float acc = subpose_tangent_dot(V0, lin, ang, times[p], v_out + 16 * p, t);
+    if (TIMES && t == 18) v_times[p] = acc;
+    else sp_part[p * 18 + t] = acc;
   }
   __syncthreads();
   if (threadIdx.x < 18) {
@@ -1197,8 +1195,8 @@ GS_EXPORT int gs_subpose_viewmats_bwd(int P, const float* viewmat, const float* 
                                       const float* times, const float* v_out, float* v_viewmat, float* v_lin,
                                       float* v_ang, void* stream) {
   if (P <= 0) return GS_ERR_INVALID;
-  hipLaunchKernelGGL(subpose_bwd_kernel, dim3(1), dim3(256), (size_t)P * 18 * sizeof(float), (hipStream_t)stream, P, viewmat, lin_vel,
-                     ang_vel, times, v_out, v_viewmat, v_lin, v_ang, 0);
+  hipLaunchKernelGGL(subpose_bwd_kernel<false>, dim3(1), dim3(256), (size_t)P * 18 * sizeof(float), (hipStream_t)stream, P, viewmat, lin_vel,
+                     ang_vel, times, v_out, v_viewmat, v_lin, v_ang, (float*)nullptr, 0);
   return gs_launch_status();
 }
 
@@ -1208,8 +1206,21 @@ GS_EXPORT int gs_subpose_viewmats_bwd_store(int P, const float* viewmat, const f
                                             const float* times, const float* v_out, float* v_viewmat, float* v_lin,
                                             float* v_ang, void* stream) {
   if (P <= 0 || !v_viewmat || !v_lin || !v_ang) return GS_ERR_INVALID;
-  hipLaunchKernelGGL(subpose_bwd_kernel, dim3(1), dim3(256), (size_t)P * 18 * sizeof(float), (hipStream_t)stream, P, viewmat, lin_vel,
-                     ang_vel, times, v_out, v_viewmat, v_lin, v_ang, 1);
+  hipLaunchKernelGGL(subpose_bwd_kernel<false>, dim3(1), dim3(256), (size_t)P * 18 * sizeof(float), (hipStream_t)stream, P, viewmat, lin_vel,
+                     ang_vel, times, v_out, v_viewmat, v_lin, v_ang, (float*)nullptr, 1);
+  return gs_launch_status();
+}
+
+// gs_subpose_viewmats_bwd_store plus the gradient of the sub-pose TIMES: v_times[p] = <v_out[p], d V_p / d t_p> over rows
+// 0..2 (d V_p / d t_p = -xi^ V_p).  All 22 + P floats are stored; v_viewmat / v_lin / v_ang hold the bits of
+// gs_subpose_viewmats_bwd_store (same one-block kernel, same per-tangent sums in sub-pose order), v_times has one writer
+// per element and no reduction.
+GS_EXPORT int gs_subpose_viewmats_bwd_times(int P, const float* viewmat, const float* lin_vel, const float* ang_vel,
+                                            const float* times, const float* v_out, float* v_viewmat, float* v_lin,
+                                            float* v_ang, float* v_times, void* stream) {
+  if (P <= 0 || !v_viewmat || !v_lin || !v_ang || !v_times) return GS_ERR_INVALID;
+  hipLaunchKernelGGL(subpose_bwd_kernel<true>, dim3(1), dim3(256), (size_t)P * 18 * sizeof(float), (hipStream_t)stream, P, viewmat, lin_vel,
+                     ang_vel, times, v_out, v_viewmat, v_lin, v_ang, v_times, 1);
   return gs_launch_status();
 }
 

@@ -35,6 +35,22 @@ class CameraVelocityOptimizerConfig:
     zero_initial_velocities: bool = False  # train.py:70
 
 
+SHUTTER_EXPOSURE_MODES = ("off", "global", "per_camera")
+SHUTTER_READOUT_MODES = ("off", "global")
+
+
+@dataclass
+class CameraShutterOptimizerConfig:
+    """learnable exposure / rolling-shutter readout times: log-scale adjustments, zero at the start, on the
+    camera's metadata values — E = E0 * exp(adj), T = T0 * exp(adj).  SE(3) motion model only."""
+    exposure: str = "off"                  # "off" | "global" (one adjustment) | "per_camera" (one per cam_idx)
+    readout: str = "off"                   # "off" | "global"
+    # starting values for cameras whose metadata holds 0 / nothing, used ONLY for a quantity that is being optimised
+    # (a zero time has no gradient direction in a log parametrisation: metadata 0 and no fallback is a ValueError)
+    initial_exposure_time: Optional[float] = None
+    initial_rolling_shutter_time: Optional[float] = None
+
+
 @dataclass
 class SplatfactoDeblurConfig:
     sh_degree: int = 3
@@ -66,6 +82,8 @@ class SplatfactoDeblurConfig:
     pixel_velocity_lists: str = "per_sample"
     camera_optimizer: CameraOptimizerConfig = field(default_factory=CameraOptimizerConfig)
     camera_velocity_optimizer: CameraVelocityOptimizerConfig = field(default_factory=CameraVelocityOptimizerConfig)
+    # learnable exposure / readout times; "off"/"off": no parameter, no optimizer, the host schedule as it always was
+    camera_shutter_optimizer: CameraShutterOptimizerConfig = field(default_factory=CameraShutterOptimizerConfig)
     # "adam": every Gaussian row steps every iteration (torch.optim.Adam); "selective_adam": only the rows the step's
     # views reached (gsplat's SelectiveAdam) — the others keep parameter and both moments unchanged
     optimizer: str = "adam"
@@ -166,6 +184,18 @@ class SplatfactoDeblurModel(nn.Module):
             self.velocity_adjustment = nn.Parameter(torch.zeros(num_cameras, 6))
         else:
             self.velocity_adjustment = None
+        sh = config.camera_shutter_optimizer
+        if sh.exposure not in SHUTTER_EXPOSURE_MODES:
+            raise ValueError(f"unknown camera_shutter_optimizer.exposure {sh.exposure!r} (one of {SHUTTER_EXPOSURE_MODES})")
+        if sh.readout not in SHUTTER_READOUT_MODES:
+            raise ValueError(f"unknown camera_shutter_optimizer.readout {sh.readout!r} (one of {SHUTTER_READOUT_MODES})")
+        if (sh.exposure != "off" or sh.readout != "off") and config.motion_model == "pixel_velocity":
+            raise ValueError("camera_shutter_optimizer needs motion_model='se3': the pixel-velocity model takes the "
+                             "sub-pose times inside its projection and compositors, which return no time gradient")
+        # log-scale adjustments, zero at the start: "per_camera" rows are indexed by metadata['cam_idx']
+        self.exposure_adjustment = (None if sh.exposure == "off" else
+                                    nn.Parameter(torch.zeros(num_cameras if sh.exposure == "per_camera" else 1)))
+        self.readout_adjustment = None if sh.readout == "off" else nn.Parameter(torch.zeros(1))
         if config.use_bilateral_grid:
             from . import bilagrid
             self.bilateral_grids = nn.Parameter(bilagrid.identity_grids(num_cameras, config.grid_shape))
@@ -296,8 +326,8 @@ class SplatfactoDeblurModel(nn.Module):
         cfg = self.config
         S = cfg.blur_samples if cfg.blur_samples > 0 else 1
         R = cfg.rs_bands if cfg.rolling_shutter_compensation else 1
-        exposure = float(camera.metadata.get("exposure_time", 0.0))
-        readout = float(camera.metadata.get("rolling_shutter_time", 0.0))
+        # (with the shutter optimizer: the effective STARTING values, fallbacks included, decide S = 1 / R = 1)
+        exposure, readout = self._base_times(camera)
         if exposure == 0.0:
             S = 1
         if readout == 0.0:
@@ -316,6 +346,49 @@ class SplatfactoDeblurModel(nn.Module):
             raise ValueError(f"unknown pixel_velocity_lists {cfg.pixel_velocity_lists!r}")
         times, _, _ = ops.subpose_schedule(S, exposure, R, readout)
         return S, R, times
+
+    def _base_times(self, camera: Camera) -> Tuple[float, float]:
+        """(E0, T0): the camera's metadata exposure / rolling-shutter time; for a quantity the shutter optimizer learns, a
+        metadata value of 0 (or none) is replaced by camera_shutter_optimizer.initial_*, and 0 there too is a ValueError"""
+        exposure = float(camera.metadata.get("exposure_time", 0.0))
+        readout = float(camera.metadata.get("rolling_shutter_time", 0.0))
+        sh = self.config.camera_shutter_optimizer
+        if self.exposure_adjustment is not None and exposure == 0.0:
+            exposure = float(sh.initial_exposure_time or 0.0)
+            if exposure == 0.0:
+                raise ValueError("camera_shutter_optimizer.exposure is on, the camera's exposure_time is 0 / absent and "
+                                 "initial_exposure_time gives no start: E = E0 * exp(adj) cannot leave 0")
+        if self.readout_adjustment is not None and readout == 0.0:
+            readout = float(sh.initial_rolling_shutter_time or 0.0)
+            if readout == 0.0:
+                raise ValueError("camera_shutter_optimizer.readout is on, the camera's rolling_shutter_time is 0 / absent "
+                                 "and initial_rolling_shutter_time gives no start: T = T0 * exp(adj) cannot leave 0")
+        return exposure, readout
+
+    def shutter_times(self, camera: Camera) -> Tuple[Tensor, Tensor]:
+        """the effective (exposure, readout) of `camera` as 0-d tensors on the parameters' device: E0 * exp(adjustment)
+        for a learned quantity (differentiable), the base value otherwise.  A "per_camera" exposure adjustment applies
+        to cam_idx inside [0, num_cameras); a camera without one renders with E0."""
+        E0, T0 = self._base_times(camera)
+        E, T = self._const([E0]).reshape(()), self._const([T0]).reshape(())
+        if self.exposure_adjustment is not None:
+            if self.config.camera_shutter_optimizer.exposure == "per_camera":
+                idx = camera.metadata.get("cam_idx") if camera.metadata else None
+                if idx is not None and 0 <= int(idx) < int(self.exposure_adjustment.shape[0]):
+                    E = E * torch.exp(self.exposure_adjustment[int(idx)])
+            else:
+                E = E * torch.exp(self.exposure_adjustment[0])
+        if self.readout_adjustment is not None:
+            T = T * torch.exp(self.readout_adjustment[0])
+        return E, T
+
+    def _times_tensor(self, camera: Camera, S: int, R: int, times) -> Tensor:
+        """the sub-pose times on the device: the cached host schedule, or — shutter optimizer on — ops.subpose_times of
+        the learned exposure / readout (differentiable)"""
+        if self.exposure_adjustment is None and self.readout_adjustment is None:
+            return self._const(times)
+        E, T = self.shutter_times(camera)
+        return ops.subpose_times(S, E, R, T, device=self.means.device)
 
     def _rs_time(self, camera: Camera) -> float:
         """readout time handed to the exact rolling-shutter compositors (0: off)"""
@@ -370,7 +443,7 @@ class SplatfactoDeblurModel(nn.Module):
             camera = camera.rescaled(d)          # splatfacto: camera.rescale_output_resolution(1 / d) while training
         viewmat, lin, ang = self._viewmat_and_velocity(camera)
         S, R, times = self._schedule(camera)
-        times_t = self._const(times)
+        times_t = self._times_tensor(camera, S, R, times)
         pixvel = cfg.motion_model == "pixel_velocity"
         if not pixvel and cfg.motion_model != "se3":
             raise ValueError(f"unknown motion_model {cfg.motion_model!r}")
@@ -447,6 +520,8 @@ class SplatfactoDeblurModel(nn.Module):
             if cfg.densify_absgrad:
                 self.xy_absgrad = torch.zeros(self.num_points, 2, device=dev)
         cam_leaves = [t for t in (viewmat, lin, ang) if t.requires_grad]
+        times_t = None if shared else self._times_tensor(camera, S, R, times)
+        times_grad = times_t is not None and times_t.requires_grad      # (the shutter optimizer: SE(3) only)
 
         def v_rgb(rgb):
             # get_outputs clamps rgb at 1 before the loss sees it; the clamp's backward is the mask
@@ -465,14 +540,14 @@ class SplatfactoDeblurModel(nn.Module):
 
         rgb, g, radii = render_step(
             self.means, self.scales, self.quats, self.opacities.reshape(-1), self.features_dc, viewmat.detach(),
-            lin.detach(), ang.detach(), list(times) if shared else self._const(times), bg.detach(), S, R,
+            lin.detach(), ang.detach(), list(times) if shared else (times_t.detach() if times_grad else times_t), bg.detach(), S, R,
             camera.fx, camera.fy, camera.cx, camera.cy, camera.height, camera.width, v_rgb,
             gamma=cfg.gamma if use_gamma else 1.0, min_rgb_level=cfg.min_rgb_level if use_gamma else 0.0,
             sh_degree=self.active_sh_degree(), antialiased=(cfg.rasterize_mode == "antialiased"),
             sh_rest=self.features_rest, raw_params=True, motion_model=cfg.motion_model, xy_grad_out=self.xy_grad,
             camera_grads=bool(cam_leaves), background_grad=bg.requires_grad,
             rolling_shutter_time=self._rs_time(camera) if pixvel else 0.0, shared_list=shared, hints=self._hints_of(camera),
-            grad_depth=v_depth, xy_absgrad_out=self.xy_absgrad)
+            grad_depth=v_depth, xy_absgrad_out=self.xy_absgrad, **({"times_grad": True} if times_grad else {}))
         for p, gr in ((self.means, g["means"]), (self.scales, g["scales"]), (self.quats, g["quats"]),
                       (self.opacities, g["opacities"]), (self.features_dc, g["sh"]), (self.features_rest, g["sh_rest"])):
             gr = gr.view_as(p)
@@ -485,6 +560,10 @@ class SplatfactoDeblurModel(nn.Module):
         if bg.requires_grad and g["background"] is not None:
             roots.append(bg)
             seeds.append(g["background"].view_as(bg))
+        if times_grad and g["times"] is not None:
+            # d loss / d times [P] into the graph of ops.subpose_times: exposure / readout adjustments
+            roots.append(times_t)
+            seeds.append(g["times"].view_as(times_t))
         if roots:
             torch.autograd.backward(roots, seeds)
         self.radii = radii
@@ -522,7 +601,7 @@ class SplatfactoDeblurModel(nn.Module):
         vms = []
         for cam, _, _, times in items:
             viewmat, lin, ang = self._viewmat_and_velocity(cam)
-            vms.append(ops.subpose_viewmats(viewmat, lin, ang, self._const(times)))
+            vms.append(ops.subpose_viewmats(viewmat, lin, ang, self._times_tensor(cam, S, R, times)))
         viewmats = torch.stack(vms)
         gp = (self.means, self.scales, self.quats, self.opacities, self.features_dc, self.features_rest)
         if detach_gaussians:

@@ -1249,6 +1249,7 @@ class _SubposeViewmats(Function):
         _check(_L().gs_subpose_viewmats_fwd(P, _ptr(V), _ptr(lin), _ptr(ang), _ptr(times), _ptr(out), _stream()),
                "subpose_viewmats_fwd")
         ctx.save_for_backward(V, lin, ang, times)
+        ctx.times_shape = tuple(times.shape)
         return out
 
     @staticmethod
@@ -1256,6 +1257,15 @@ class _SubposeViewmats(Function):
         V, lin, ang, times = ctx.saved_tensors
         P = times.numel()
         dev = V.device
+        if ctx.needs_input_grad[3]:
+            # learnable exposure / readout times (subpose_times): the same kernel with a 19th tangent per sub-pose; the 22
+            # camera floats hold the bits of the path below, v_times [P] has one writer per element
+            acc = torch.empty(22 + P, device=dev)
+            v_V, v_lin, v_ang, v_times = acc[:16].view(4, 4), acc[16:19], acc[19:22], acc[22:]
+            _check(_L().gs_subpose_viewmats_bwd_times(P, _ptr(V), _ptr(lin), _ptr(ang), _ptr(times),
+                                                      _ptr(v_out.contiguous().float()), _ptr(v_V), _ptr(v_lin), _ptr(v_ang),
+                                                      _ptr(v_times), _stream()), "subpose_viewmats_bwd_times")
+            return v_V, v_lin, v_ang, v_times.view(ctx.times_shape)
         acc = torch.empty(22, device=dev)                  # the one-block kernel stores all 22 floats: no fill launch
         v_V, v_lin, v_ang = acc[:16].view(4, 4), acc[16:19], acc[19:22]
         _check(_L().gs_subpose_viewmats_bwd_store(P, _ptr(V), _ptr(lin), _ptr(ang), _ptr(times),
@@ -1282,6 +1292,44 @@ def subpose_schedule(blur_samples: int, exposure_time: float, rs_bands: int, rol
             samp.append(s)
             band.append(r)
     return times, samp, band
+
+
+_TIME_COEFS: dict = {}
+
+
+def subpose_time_coefficients(blur_samples: int, rs_bands: int, device=None):
+    """(coef_e [P], coef_r [P]) float32 on `device`, cached per (S, R, device): the sub-pose times are
+    coef_e * exposure + coef_r * readout with coef_e[p] = (s+.5)/S - .5 (0 for S = 1), coef_r[p] = (r+.5)/R - .5
+    (0 for R = 1), p = s*R + r — subpose_schedule's formula with the two times factored out."""
+    S, R = max(1, int(blur_samples)), max(1, int(rs_bands))
+    dev = torch.device("cpu") if device is None else torch.device(device)
+    key = (S, R, str(dev))
+    hit = _TIME_COEFS.get(key)
+    if hit is None:
+        ce = [(((s + 0.5) / S - 0.5) if S > 1 else 0.0) for s in range(S) for _ in range(R)]
+        cr = [(((r + 0.5) / R - 0.5) if R > 1 else 0.0) for _ in range(S) for r in range(R)]
+        hit = _TIME_COEFS[key] = (torch.tensor(ce, dtype=torch.float64).to(dev), torch.tensor(cr, dtype=torch.float64).to(dev),
+                                  torch.tensor(ce, dtype=torch.float32, device=dev),
+                                  torch.tensor(cr, dtype=torch.float32, device=dev))
+    return hit[2], hit[3]
+
+
+def subpose_times(blur_samples: int, exposure, rs_bands: int, readout, device=None) -> Tensor:
+    """The tensor twin of subpose_schedule: times [P] = coef_e * exposure + coef_r * readout (p = s*R + r), float32 on
+    `device`, differentiable in both times — what learnable exposure / readout times are rendered through
+    (subpose_viewmats carries d loss / d times back: gs_subpose_viewmats_bwd_times).  exposure, readout: 0-d tensors or
+    floats.  For two floats the sum is formed in float64 and cast once, so the values are subpose_schedule's after the
+    fp32 cast; a tensor input is float32 arithmetic: cast(coef) * E + cast(coef) * T."""
+    ce, cr = subpose_time_coefficients(blur_samples, rs_bands, device)
+    if not isinstance(exposure, Tensor) and not isinstance(readout, Tensor):
+        ce64, cr64 = _TIME_COEFS[(max(1, int(blur_samples)), max(1, int(rs_bands)), str(ce.device))][:2]
+        return (ce64 * float(exposure) + cr64 * float(readout)).to(torch.float32)
+
+    def scalar(x):
+        if isinstance(x, Tensor):
+            return x.to(device=ce.device, dtype=torch.float32).reshape(())
+        return torch.tensor(float(x), dtype=torch.float32, device=ce.device)
+    return ce * scalar(exposure) + cr * scalar(readout)
 
 
 # --------------------------------------------------------------------------- #

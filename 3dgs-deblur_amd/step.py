@@ -47,7 +47,7 @@ def render_step(means: Tensor, scales: Tensor, quats: Tensor, opacities: Tensor,
                 background_grad: bool = False, glob_scale: float = 1.0, clip_thresh: float = 0.01,
                 rolling_shutter_time: float = 0.0, shared_list: bool = False, hints: Optional["ops.FrameHints"] = None,
                 grad_depth: Optional[Union[Tensor, Callable[[Tensor, Tensor], Tuple[Tensor, Optional[Tensor]]]]] = None,
-                xy_absgrad_out: Optional[Tensor] = None
+                xy_absgrad_out: Optional[Tensor] = None, times_grad: bool = False
                 ) -> Tuple[Tensor, Dict[str, Optional[Tensor]], Tensor]:
     """One frame, forward and backward.  Arguments as ops.render_combined (raw_params: log-scales / opacity logits;
     sh_rest: features_rest beside sh = features_dc), but the camera comes as ONE mid-exposure `viewmat` [4,4] + body
@@ -61,7 +61,11 @@ def render_step(means: Tensor, scales: Tensor, quats: Tensor, opacities: Tensor,
     (d loss / d depth_acc, d loss / d alphas or None), invoked between the two halves like grad_image — a loss on the
     expected depth depth_acc / alpha needs the alpha term (SplatfactoDeblurModel.render_and_backward does that chain).
     xy_absgrad_out (optional float32 [N,2], motion_model "se3" only): OVERWRITTEN with the absgrad statistic, as in
-    ops.render_subposes; the pixel-velocity model raises ValueError before any launch."""
+    ops.render_subposes; the pixel-velocity model raises ValueError before any launch.
+    times_grad=True (motion_model "se3" only): the gradient dict gains "times" [P], d loss / d times, from the same
+    sub-pose backward call (gs_subpose_viewmats_bwd_times; the other camera gradients keep their bits).  The
+    pixel-velocity model, the shared list and exact rolling shutter raise ValueError before any launch — the times enter
+    their projection and compositors, not subpose_viewmats.  False: exactly the keys listed above."""
     S, R = max(1, int(blur_samples)), max(1, int(rs_bands))
     pixvel = motion_model == "pixel_velocity"
     if not pixvel and motion_model != "se3":
@@ -69,13 +73,16 @@ def render_step(means: Tensor, scales: Tensor, quats: Tensor, opacities: Tensor,
     if pixvel and xy_absgrad_out is not None:
         raise ValueError("xy_absgrad_out is not available with the pixel-velocity model: its backward compositor uses "
                          "gradient slots 9 and 10 for d loss / d pixel velocity")
+    if times_grad and (pixvel or shared_list or float(rolling_shutter_time) != 0.0):
+        raise ValueError("times_grad is available with the SE(3) motion model only: the pixel-velocity model, the shared "
+                         "list and exact rolling shutter take the sub-pose times inside their projection / compositors")
     sub_ctx = None
     if pixvel:
         vms = viewmat
     else:
-        sub_ctx = _Ctx((camera_grads, camera_grads, camera_grads, False))
+        sub_ctx = _Ctx((camera_grads, camera_grads, camera_grads, bool(times_grad)))
         vms = ops._SubposeViewmats.forward(sub_ctx, viewmat, lin_vel, ang_vel, times)
-    needs = [True, True, True, True, True, camera_grads, background is not None and background_grad] + [False] * 16 + \
+    needs = [True, True, True, True, True, camera_grads or bool(times_grad), background is not None and background_grad] + [False] * 16 + \
             [camera_grads and pixvel, camera_grads and pixvel, False, False, False, sh_rest is not None, False, False]
     ctx = _Ctx(needs)
     depth = grad_depth is not None
@@ -110,8 +117,14 @@ def render_step(means: Tensor, scales: Tensor, quats: Tensor, opacities: Tensor,
     g = ops._RenderSubposes.backward(ctx, v_rgb, v_alpha, None, v_depth)
     grads = {"means": g[0], "scales": g[1], "quats": g[2], "opacities": g[3], "sh": g[4], "background": g[6],
              "sh_rest": g[28], "viewmat": None, "lin_vel": None, "ang_vel": None}
+    if times_grad:
+        grads["times"] = None
     if pixvel:
         grads["viewmat"], grads["lin_vel"], grads["ang_vel"] = g[5], g[23], g[24]
-    elif camera_grads and g[5] is not None:
-        grads["viewmat"], grads["lin_vel"], grads["ang_vel"], _ = ops._SubposeViewmats.backward(sub_ctx, g[5])
+    elif (camera_grads or times_grad) and g[5] is not None:
+        v_V, v_lin, v_ang, v_times = ops._SubposeViewmats.backward(sub_ctx, g[5])
+        if camera_grads:
+            grads["viewmat"], grads["lin_vel"], grads["ang_vel"] = v_V, v_lin, v_ang
+        if times_grad:
+            grads["times"] = v_times
     return rgb, grads, radii

@@ -116,9 +116,10 @@ def mcmc_regularization(opacity_logits: Tensor, log_scales: Tensor, opacity_reg:
 
 def _small_params(model: SplatfactoDeblurModel):
     """the parameters that are not per-Gaussian rows — learnable background, pose / velocity adjustments, bilateral
-    grids: under data parallelism their gradients travel in one small dense bucket"""
+    grids, exposure / readout adjustments: under data parallelism their gradients travel in one small dense bucket"""
     return [p for p in (model.background_param, model.pose_adjustment, model.velocity_adjustment,
-                        getattr(model, "bilateral_grids", None)) if p is not None]
+                        getattr(model, "bilateral_grids", None), getattr(model, "exposure_adjustment", None),
+                        getattr(model, "readout_adjustment", None)) if p is not None]
 
 
 def _grid_tv(model: SplatfactoDeblurModel) -> Optional[Tensor]:
@@ -189,6 +190,14 @@ class SelectiveAdam(torch.optim.Optimizer):
 
 
 OPTIMIZERS = ("adam", "selective_adam")
+# learning rate of the "camera_shutter_opt" group (log-seconds per step): measured, DESIGN §5.9
+SHUTTER_LR = 1e-3
+
+
+def shutter_params(model: SplatfactoDeblurModel):
+    """the exposure / readout adjustments the model holds (SplatfactoDeblurConfig.camera_shutter_optimizer), in that order"""
+    return [p for p in (getattr(model, "exposure_adjustment", None), getattr(model, "readout_adjustment", None))
+            if p is not None]
 SELECTIVE_MASKS = ("visible", "touched")
 
 
@@ -225,6 +234,10 @@ def make_optimizers(model: SplatfactoDeblurModel, lr_scale: float = 1.0,
         # splatfacto's bilateral_grid group (2e-3, eps 1e-15); upstream warms it up and decays it — this trainer has no
         # schedulers
         opts["bilateral_grid"] = Adam([model.bilateral_grids], lr=2e-3 * lr_scale, eps=1e-15)
+    shutter = shutter_params(model)
+    if shutter:
+        # learnable exposure / readout times (log-scale adjustments): one dense group for whichever exist
+        opts["camera_shutter_opt"] = Adam(shutter, lr=SHUTTER_LR * lr_scale, eps=1e-15)
     return opts
 
 
@@ -453,7 +466,10 @@ def eval_camera_step(model: SplatfactoDeblurModel, optimizers: Dict[str, torch.o
                      gt_image: Tensor, ssim_lambda: float = 0.2) -> float:
     """`--optimize-eval-cameras` (/root/reference/train.py:180-183, README.md:197): one step on an EVALUATION frame
     in which only its pose / velocity adjustment is updated — the Gaussians are constants (no gradient reaches them,
-    their optimizers do not step)."""
+    their optimizers do not step).  The shutter optimizer's exposure / readout adjustments do NOT step either: an
+    evaluation frame must not move a global shutter estimate (it renders WITH the learned times; what gradient it
+    leaves on the two parameters is cleared before returning, and "per_camera" exposure rows of evaluation cameras
+    therefore stay 0)."""
     model.train()
     cam_opts = [optimizers[k] for k in ("camera_opt", "camera_velocity_opt") if k in optimizers]
     if not cam_opts:
@@ -467,6 +483,8 @@ def eval_camera_step(model: SplatfactoDeblurModel, optimizers: Dict[str, torch.o
     loss = image_loss(out["rgb"], gt_image, ssim_lambda)
     loss.backward()
     optimizers_step(cam_opts)
+    for p in shutter_params(model):
+        p.grad = None
     return float(loss.item())
 
 

@@ -69,6 +69,14 @@ int gs_subpose_viewmats_bwd(int P, const float* viewmat, const float* lin_vel, c
 int gs_subpose_viewmats_bwd_store(int P, const float* viewmat, const float* lin_vel, const float* ang_vel,
                                   const float* times, const float* v_out /*P*16*/, float* v_viewmat,
                                   float* v_lin, float* v_ang, void* stream);
+/* gs_subpose_viewmats_bwd_store plus the gradient of the sub-pose TIMES: v_times[p] = sum over the 12 entries of rows
+ * 0..2 of v_out[p][j] * dV_p[j]/dt_p (dV_p/dt_p = -xi^ V_p, xi^ = [[ang]x lin; 0 0]).  All 22 + P floats are stored
+ * (nothing to zero); v_viewmat, v_lin, v_ang hold exactly the bits gs_subpose_viewmats_bwd_store writes; v_times has one
+ * writer per element and no reduction over p.  P <= 0 or a null output: GS_ERR_INVALID.  What learnable exposure and
+ * readout times are trained through (SplatfactoDeblurConfig.camera_shutter_optimizer). */
+int gs_subpose_viewmats_bwd_times(int P, const float* viewmat, const float* lin_vel, const float* ang_vel,
+                                  const float* times, const float* v_out /*P*16*/, float* v_viewmat /*16*/,
+                                  float* v_lin /*3*/, float* v_ang /*3*/, float* v_times /*P*/, void* stream);
 
 /* ---- gsplat.project_gaussians (upstream _C.project_gaussians_forward/backward; SURVEY §8 a1,a3)
  * needed by: train.py:40 (camera-optimizer => viewmat grads), train.py:119 (antialiased => comp). */

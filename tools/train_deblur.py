@@ -9,7 +9,8 @@ Variants follow /root/reference/train.py:29-76: blur_samples 0 = no motion-blur 
 5 (the default, train.py:46) and 10 (synthetic sets, train.py:22); --motion-model picks the SE(3) re-projection
 (north_star) or the paper's pixel-velocity model; --optimize-eval-cameras refines the evaluation poses without
 touching the Gaussians (train.py:180-183); --densify adds splatfacto's refinement schedule or 3DGS-MCMC (--cap-max);
---bilateral-grid learns a per-image colour correction with the scene.  Every variant leaves checkpoint_<name>.pt beside
+--bilateral-grid learns a per-image colour correction with the scene; --optimize-exposure / --optimize-readout learn the
+exposure and rolling-shutter readout times from their metadata values.  Every variant leaves checkpoint_<name>.pt beside
 its metrics_<name>.json (--checkpoint-every K: also every K steps; --resume PATH continues from one; --export-ply adds
 splat_<name>.ply for a viewer); tools/render_model.py renders either file."""
 import argparse
@@ -54,6 +55,11 @@ def main():
     ap.add_argument("--bilateral-grid", action="store_true",
                     help="per-image bilateral-grid colour correction of the training renders (exposure / white-balance "
                          "drift); evaluation renders are never corrected")
+    ap.add_argument("--optimize-exposure", default=None, choices=["global", "per_camera"],
+                    help="learn the exposure time (one log-scale adjustment for the scene, or one per training camera) "
+                         "from the metadata value; SE(3) motion model only")
+    ap.add_argument("--optimize-readout", action="store_true",
+                    help="learn the rolling-shutter readout time (one log-scale adjustment) from the metadata value")
     ap.add_argument("--checkpoint-every", type=int, default=0,
                     help="also write checkpoint_<name>.pt every K steps (it is always written after the last step)")
     ap.add_argument("--resume", default=None,
@@ -98,6 +104,10 @@ def main():
             dcfg = gs.mcmc.MCMCConfig(cap_max=args.cap_max, refine_stop_iter=int(0.9 * args.iterations))
         if args.optimize_eval_cameras:
             cfg.camera_optimizer.mode = "SO3xR3"
+        if args.optimize_exposure:
+            cfg.camera_shutter_optimizer.exposure = args.optimize_exposure
+        if args.optimize_readout:
+            cfg.camera_shutter_optimizer.readout = "global"
         model = SD.init_from_seed_points(cfg, xyz, rgb, dev, num_cameras=len(scene.cameras))
         name = (f"blur_samples_{bs}" + ("_pixvel" if args.motion_model == "pixel_velocity" else "") +
                 ("" if args.rolling_shutter_time <= 0 else f"_rs_{args.rolling_shutter_mode}"))
