@@ -13,7 +13,9 @@ from __future__ import annotations
 
 import ctypes
 import math
-from typing import Optional, Tuple
+from collections import namedtuple
+from dataclasses import dataclass
+from typing import NamedTuple, Optional, Tuple
 
 import torch
 from torch import Tensor
@@ -528,18 +530,6 @@ def _band_edges(img_height: int, rs_bands: int, device) -> Tensor:
         if len(_band_edge_cache) > 64:
             _band_edge_cache.clear()
         _band_edge_cache[key] = t
-    return t
-
-
-_placeholder_cache = {}
-
-
-def _placeholder_i32(dev) -> Tensor:
-    """a one-element int32 tensor per device for save_for_backward slots that hold nothing (a fresh torch.zeros is a
-    fill launch per frame, issued on the host's critical path behind the last read-back)"""
-    t = _placeholder_cache.get(str(dev))
-    if t is None:
-        t = _placeholder_cache[str(dev)] = torch.zeros(1, dtype=torch.int32, device=dev)
     return t
 
 
@@ -1239,39 +1229,50 @@ def bin_and_sort_gaussians(num_points: int, num_intersects: int, xys: Tensor, de
 # --------------------------------------------------------------------------- #
 # sub-pose viewmats (SE(3) screw interpolation)
 # --------------------------------------------------------------------------- #
+def subpose_forward(viewmat, lin_vel, ang_vel, times):
+    """-> (viewmats [P,4,4], saved = (V, lin, ang, times) for subpose_backward); knows nothing about autograd"""
+    V = _viewmat16(viewmat)
+    lin, ang, times = _f32(lin_vel, "lin_vel"), _f32(ang_vel, "ang_vel"), _f32(times, "times")
+    P = times.numel()
+    out = torch.empty(P, 4, 4, device=V.device)
+    _check(_L().gs_subpose_viewmats_fwd(P, _ptr(V), _ptr(lin), _ptr(ang), _ptr(times), _ptr(out), _stream()),
+           "subpose_viewmats_fwd")
+    return out, (V, lin, ang, times)
+
+
+def subpose_backward(saved, v_out, want_times: bool):
+    """-> (v_viewmat [4,4], v_lin_vel [3], v_ang_vel [3], v_times in the shape of times, or None without want_times)"""
+    V, lin, ang, times = saved
+    P = times.numel()
+    dev = V.device
+    if want_times:
+        # learnable exposure / readout times (subpose_times): the same kernel with a 19th tangent per sub-pose; the 22
+        # camera floats hold the bits of the path below, v_times [P] has one writer per element
+        acc = torch.empty(22 + P, device=dev)
+        v_V, v_lin, v_ang, v_times = acc[:16].view(4, 4), acc[16:19], acc[19:22], acc[22:]
+        _check(_L().gs_subpose_viewmats_bwd_times(P, _ptr(V), _ptr(lin), _ptr(ang), _ptr(times),
+                                                  _ptr(v_out.contiguous().float()), _ptr(v_V), _ptr(v_lin), _ptr(v_ang),
+                                                  _ptr(v_times), _stream()), "subpose_viewmats_bwd_times")
+        return v_V, v_lin, v_ang, v_times.view(times.shape)
+    acc = torch.empty(22, device=dev)                  # the one-block kernel stores all 22 floats: no fill launch
+    v_V, v_lin, v_ang = acc[:16].view(4, 4), acc[16:19], acc[19:22]
+    _check(_L().gs_subpose_viewmats_bwd_store(P, _ptr(V), _ptr(lin), _ptr(ang), _ptr(times),
+                                              _ptr(v_out.contiguous().float()), _ptr(v_V), _ptr(v_lin), _ptr(v_ang),
+                                              _stream()), "subpose_viewmats_bwd_store")
+    return v_V, v_lin, v_ang, None
+
+
 class _SubposeViewmats(Function):
     @staticmethod
     def forward(ctx, viewmat, lin_vel, ang_vel, times):
-        V = _viewmat16(viewmat)
-        lin, ang, times = _f32(lin_vel, "lin_vel"), _f32(ang_vel, "ang_vel"), _f32(times, "times")
-        P = times.numel()
-        out = torch.empty(P, 4, 4, device=V.device)
-        _check(_L().gs_subpose_viewmats_fwd(P, _ptr(V), _ptr(lin), _ptr(ang), _ptr(times), _ptr(out), _stream()),
-               "subpose_viewmats_fwd")
-        ctx.save_for_backward(V, lin, ang, times)
-        ctx.times_shape = tuple(times.shape)
+        out, saved = subpose_forward(viewmat, lin_vel, ang_vel, times)
+        ctx.save_for_backward(*saved)
         return out
 
     @staticmethod
     def backward(ctx, v_out):
-        V, lin, ang, times = ctx.saved_tensors
-        P = times.numel()
-        dev = V.device
-        if ctx.needs_input_grad[3]:
-            # learnable exposure / readout times (subpose_times): the same kernel with a 19th tangent per sub-pose; the 22
-            # camera floats hold the bits of the path below, v_times [P] has one writer per element
-            acc = torch.empty(22 + P, device=dev)
-            v_V, v_lin, v_ang, v_times = acc[:16].view(4, 4), acc[16:19], acc[19:22], acc[22:]
-            _check(_L().gs_subpose_viewmats_bwd_times(P, _ptr(V), _ptr(lin), _ptr(ang), _ptr(times),
-                                                      _ptr(v_out.contiguous().float()), _ptr(v_V), _ptr(v_lin), _ptr(v_ang),
-                                                      _ptr(v_times), _stream()), "subpose_viewmats_bwd_times")
-            return v_V, v_lin, v_ang, v_times.view(ctx.times_shape)
-        acc = torch.empty(22, device=dev)                  # the one-block kernel stores all 22 floats: no fill launch
-        v_V, v_lin, v_ang = acc[:16].view(4, 4), acc[16:19], acc[19:22]
-        _check(_L().gs_subpose_viewmats_bwd_store(P, _ptr(V), _ptr(lin), _ptr(ang), _ptr(times),
-                                                  _ptr(v_out.contiguous().float()), _ptr(v_V), _ptr(v_lin), _ptr(v_ang),
-                                                  _stream()), "subpose_viewmats_bwd_store")
-        return v_V, v_lin, v_ang, None
+        *_, want_times = ctx.needs_input_grad             # (viewmat, lin_vel, ang_vel, times)
+        return subpose_backward(ctx.saved_tensors, v_out, want_times)
 
 
 def subpose_viewmats(viewmat: Tensor, lin_vel: Tensor, ang_vel: Tensor, times: Tensor) -> Tensor:
@@ -1335,373 +1336,443 @@ def subpose_times(blur_samples: int, exposure, rs_bands: int, readout, device=No
 # --------------------------------------------------------------------------- #
 # fused multi-sub-pose render
 # --------------------------------------------------------------------------- #
+# the tensors of a frame that can carry a gradient, in the ONE order the autograd node takes them, frame_forward names
+# them and FrameGrads returns their gradients
+FRAME_TENSORS = ("means", "scales", "quats", "opacities", "sh", "sh_rest", "viewmats", "background", "lin_vel",
+                 "ang_vel")
+FrameGrads = namedtuple("FrameGrads", FRAME_TENSORS, defaults=[None] * len(FRAME_TENSORS))
+# which gradients a frame is asked for: a frozenset of these names (the five Gaussian tensors and the twist go together)
+_WANT_OF = {"means": "gaussians", "scales": "gaussians", "quats": "gaussians", "opacities": "gaussians",
+            "sh": "gaussians", "sh_rest": "sh_rest", "viewmats": "viewmats", "background": "background",
+            "lin_vel": "twist", "ang_vel": "twist"}
+
+
+@dataclass(frozen=True)
+class FrameSpec:
+    """every non-tensor input of a frame.  S, R: blur samples (of ALL cameras) and row bands; gamma None: per-sample
+    output; param_flags bit 0: log-scales, bit 1: opacity logits; cameras = B > 1 (render_batch): S and the viewmats span
+    all of them, camera b owns sample images [b*S/B, (b+1)*S/B) and sub-poses [b*P/B, (b+1)*P/B)"""
+    S: int
+    R: int
+    fx: float
+    fy: float
+    cx: float
+    cy: float
+    H: int
+    W: int
+    sh_degree: int
+    antialiased: bool
+    glob_scale: float
+    clip_thresh: float
+    gamma: Optional[float]
+    min_rgb_level: float
+    return_alpha: bool
+    return_depth: bool
+    rs_time: float
+    param_flags: int
+    shared_list: bool
+    cameras: int
+
+    @classmethod
+    def of(cls, S, R, fx, fy, cx, cy, H, W, *, sh_degree=3, antialiased=True, glob_scale=1.0, clip_thresh=0.01, gamma=None,
+           min_rgb_level=0.0, return_alpha=True, return_depth=False, rs_time=0.0, raw_params=False, shared_list=False,
+           cameras=1) -> "FrameSpec":
+        """the spec with every field in the type the C ABI takes"""
+        return cls(int(S), int(R), float(fx), float(fy), float(cx), float(cy), int(H), int(W), int(sh_degree),
+                   bool(antialiased), float(glob_scale), float(clip_thresh), None if gamma is None else float(gamma),
+                   float(min_rgb_level), bool(return_alpha), bool(return_depth), float(rs_time or 0.0),
+                   3 if raw_params else 0, bool(shared_list), max(1, int(cameras)))
+
+
+class FrameExtras(NamedTuple):
+    """what a frame takes beside its spec and its differentiable tensors"""
+    times: Optional[Tensor] = None
+    xy_grad_out: Optional[Tensor] = None
+    xy_absgrad_out: Optional[Tensor] = None
+    hints: Optional[FrameHints] = None
+
+
+# the tensors frame_backward reads beside the FrameSaved; the autograd node keeps them through save_for_backward
+FrameTensors = namedtuple("FrameTensors", "means scales quats opacities sh sh_rest V twist times records edges bg out_T "
+                                          "samples rgb")
+
+
+@dataclass
+class FrameSaved:
+    """what frame_forward hands frame_backward beside the FrameTensors"""
+    spec: FrameSpec
+    N: int
+    P: int
+    K: int
+    want: frozenset
+    bg_grad: bool
+    frame: Optional[dict]               # the native frame (arena lease + gs_frame_state), or
+    backend: object                     # the test frame backend and
+    slices: list                        # its slices
+    prealloc: Optional[dict]            # the backward's buffers issued ahead of the frame; frame_backward drops them
+    rs: Optional[tuple]
+    xy_grad_out: Optional[Tensor]
+    xy_absgrad_out: Optional[Tensor]
+
+
+def _validate_frame(*, pixvel: bool, R: int, rs_time: float, shared_list: bool, absgrad: bool, batch: bool) -> None:
+    """the combinations a frame refuses, before any device work (CPU tensors get this far)"""
+    twin = frame_backend is not None and not frame_backend.native_ok()
+    if absgrad and pixvel:
+        # the pixel-velocity compositor keeps d loss / d pixel velocity in the tuple slots absgrad uses
+        raise ValueError("xy_absgrad_out is not available with the pixel-velocity model (times=): its backward "
+                         "compositor uses gradient slots 9 and 10 for d loss / d pixel velocity")
+    if batch and pixvel:
+        raise NotImplementedError("a frame of several cameras (render_batch) renders SE(3) sub-poses; the "
+                                  "pixel-velocity model (times=) renders one camera per call (render_combined)")
+    if batch and shared_list:
+        raise NotImplementedError("render_batch has no shared-list mode (pixel-velocity model, one camera per call)")
+    if batch and twin:
+        raise NotImplementedError("render_batch runs through the library's frame path only; the Python frame backend "
+                                  "renders one camera per call")
+    if absgrad and twin:
+        raise ValueError("xy_absgrad_out needs the library's frame path (the absgrad backward compositors); the "
+                         "frame backend in use has none")
+    if rs_time != 0.0 and (not pixvel or R != 1):
+        raise ValueError("exact rolling shutter (rolling_shutter_time != 0) needs the pixel-velocity model "
+                         "(times / lin_vel / ang_vel) and rs_bands == 1")
+    if shared_list and (not pixvel or R != 1):
+        raise ValueError("shared_list needs the pixel-velocity model (times / lin_vel / ang_vel) and rs_bands == 1")
+    if shared_list and twin:
+        raise ValueError("the shared-list mode runs through the library's frame path only")
+
+
+def frame_forward(spec: FrameSpec, means, scales, quats, opacities, sh, sh_rest=None, viewmats=None, background=None,
+                  lin_vel=None, ang_vel=None, *, want=frozenset(), times=None, xy_grad_out=None, xy_absgrad_out=None,
+                  hints=None):
+    """One frame, knowing nothing about autograd: the tensors of FRAME_TENSORS by name, `want` = the gradients a later
+    frame_backward is asked for (names of _WANT_OF's values; empty: forward only), the FrameExtras by name.
+    -> ((image, alphas or None, radii, depth_acc or None), FrameSaved, FrameTensors)"""
+    S, R, H, W, B = spec.S, spec.R, spec.H, spec.W, spec.cameras
+    # pixel-velocity model: ONE mid-exposure viewmat + the camera twist + the P sub-pose times
+    pixvel = times is not None
+    rs_time = spec.rs_time
+    _validate_frame(pixvel=pixvel, R=R, rs_time=rs_time, shared_list=spec.shared_list,
+                    absgrad=xy_absgrad_out is not None, batch=B > 1)
+    means, scales, quats = _f32(means, "means3d"), _f32(scales, "scales"), _f32(quats, "quats")
+    opacities, sh = _f32(opacities, "opacities").reshape(-1), _f32(sh, "sh")
+    # raw splatfacto parameters (param_flags; sh_rest: features_rest beside sh = features_dc): activations, their
+    # backward and the SH concatenation happen inside the projection kernels
+    param_flags = spec.param_flags
+    if sh_rest is not None:
+        sh_rest = _f32(sh_rest, "sh_rest")
+        if sh.reshape(sh.shape[0], -1).shape[1] != 3 or sh_rest.dim() != 3 or sh_rest.shape[0] != sh.shape[0]:
+            raise ValueError("with sh_rest [N,K-1,3], sh must be features_dc [N,3] (or [N,1,3])")
+    xy_shape = (means.shape[0], 2) if B == 1 else (B, means.shape[0], 2)
+    for name, out in (("xy_grad_out", xy_grad_out), ("xy_absgrad_out", xy_absgrad_out)):
+        if out is not None and (out.shape != xy_shape or out.dtype != torch.float32 or not out.is_contiguous()
+                                or out.device != means.device):
+            raise ValueError(f"{name} must be a contiguous float32 {list(xy_shape)} tensor on the Gaussians' device")
+    N, K = means.shape[0], (sh.shape[1] if sh_rest is None else 1 + sh_rest.shape[1])
+    P = S * R
+    if P > MAX_SUBPOSES:
+        raise ValueError(f"{S} blur samples x {R} row bands = {P} sub-poses per frame; the slice descriptors travel "
+                         f"in kernel arguments and hold at most {MAX_SUBPOSES} (kMaxSubposes, csrc/binning.hip)")
+    # shared list (pixel-velocity model, rs_bands == 1): ONE record set, depth sort and tile list for the frame —
+    # the splats at the centre of the sampled time span, tile boxes swept over the whole span (+ readout); the
+    # compositor evaluates sample s at xy + (times[s] - centre + tau(y)) * pixel_velocity
+    shared = None
+    if spec.shared_list:
+        tl = [float(t) for t in (times.reshape(-1).tolist() if isinstance(times, Tensor) else times)]
+        if len(tl) != S:
+            raise ValueError(f"times must hold {S} sample times")
+        t_c = 0.5 * (min(tl) + max(tl))
+        shared = (torch.tensor([t - t_c for t in tl], dtype=torch.float32, device=means.device),
+                  (max(tl) - min(tl)) + abs(rs_time), (min(tl) - t_c, max(tl) - t_c))
+        times = torch.tensor([t_c], dtype=torch.float32, device=means.device)
+        P = 1
+    if pixvel:
+        V = _viewmat16(viewmats).reshape(4, 4)
+        twist = torch.cat([_f32(lin_vel, "lin_vel").reshape(3), _f32(ang_vel, "ang_vel").reshape(3)]).contiguous()
+        times = _f32(times, "times").reshape(-1)
+        if times.numel() != P:
+            raise ValueError(f"times must hold {P} sub-pose times")
+    else:
+        V = _f32(viewmats, "viewmats")
+        twist = None
+        if V.shape != (P, 4, 4):
+            raise ValueError(f"viewmats must be [{P},4,4]")
+    dev = means.device
+    L = _L()
+    records = torch.empty(P * N, REC, device=dev)
+    dkeys = torch.empty(P * N, dtype=torch.int32, device=dev)
+    ntiles = torch.empty(P * N, dtype=torch.int32, device=dev)
+    radii = torch.empty(P, N, dtype=torch.int32, device=dev)
+    # bit 1: culled (Gaussian, sub-pose) pairs get no record at all.  Safe when nothing downstream looks at them:
+    # the compacting pre-sort never ranks them and the tuple backward only visits rows the compositor touched
+    # (the atomics backward of the pixel-velocity model tells "covers no tile" by an all-zero record)
+    # bit 0: SH colour deferred to the depth slices (gs_slice_colors colours only what a slice emits)
+    backend = frame_backend if (frame_backend is not None and not frame_backend.native_ok()) else None
+    defer_flags = 3 if backend is None else backend.defer_flags()
+    # bit 2 + R in bits 8..23: band-aware projection (a (band, Gaussian) pair whose tile rows miss the band is culled
+    # before the depth pre-sort instead of being keyed, sorted, scanned and planned for nothing)
+    if backend is None and R > 1 and BAND_AWARE:
+        defer_flags |= 4 | (R << 8)
+    if backend is None and hints is None:
+        # default owner of the frame-to-frame hints: the scene's shape AND its parameter storage, so that two
+        # scenes of one shape do not share a budget / arena estimate (and the camera count of a batch)
+        key = (str(dev), N, P, S, H, W, shared is not None, means.untyped_storage().data_ptr())
+        hints = hints_for(key if B == 1 else key + (B,))
+    # lazy records (see LAZY_RECORDS): SE(3) sub-poses through the library's frame path, planned slices, and a scene
+    # whose frames have so far stopped within the default budget
+    lazy = None
+    if (backend is None and not pixvel and LAZY_RECORDS and hints.slice_base() > 0
+            and (LAZY_RECORDS == 2 or hints.lazy_records())):
+        defer_flags |= 16
+    pix_vel = torch.empty(N, 2, device=dev) if (rs_time != 0.0 or shared is not None) else None
+    rs = None if pix_vel is None else (pix_vel, rs_time) + ((shared[0], shared[2]) if shared is not None else ())
+    box_sweep = shared[1] if shared is not None else rs_time      # what the projection widens the tile boxes by
+
+    def _project():
+        if pixvel:
+            _check(L.gs_project_pixvel_fwd(N, P, _ptr(means), _ptr(scales), spec.glob_scale, _ptr(quats),
+                                           _ptr(opacities), _ptr(sh), K, spec.sh_degree, _ptr(V), _ptr(twist),
+                                           _ptr(times), spec.fx, spec.fy, spec.cx, spec.cy, H, W, spec.clip_thresh,
+                                           spec.antialiased, defer_flags, _ptr(records), _ptr(dkeys), _ptr(ntiles),
+                                           _ptr(radii), box_sweep, _ptr(pix_vel), _ptr(sh_rest), param_flags, _stream()),
+                   "project_pixvel_fwd")
+        else:
+            _check(L.gs_project_fused_fwd(N, P, _ptr(means), _ptr(scales), spec.glob_scale, _ptr(quats), _ptr(opacities),
+                                          _ptr(sh), K, spec.sh_degree, _ptr(V), spec.fx, spec.fy, spec.cx, spec.cy, H, W,
+                                          spec.clip_thresh, spec.antialiased, defer_flags, _ptr(records), _ptr(dkeys),
+                                          _ptr(ntiles), _ptr(radii), _ptr(sh_rest), param_flags, _stream()),
+                   "project_fused_fwd")
+
+    with _stage("project_fwd"):
+        _project()
+    if defer_flags & 16:
+        lazy = _ProjectInputs(means.data_ptr(), scales.data_ptr(), quats.data_ptr(), opacities.data_ptr(),
+                              V.data_ptr(), spec.glob_scale, spec.fx, spec.fy, spec.cx, spec.cy, spec.clip_thresh,
+                              spec.antialiased, defer_flags & ~16, param_flags)
+    bg = _background(background, dev)
+    edges = _band_edges(H, R, dev)
+    # deferred colour: the view direction of every sub-pose (pixel-velocity model: the mid-exposure pose for all)
+    V_col = V.reshape(1, 16).expand(P, 16).contiguous() if pixvel else V
+    color = (means, sh, sh_rest, K, spec.sh_degree, V_col) if (defer_flags & 1) else None
+    # optional fourth channel: sum of weight * camera-space depth per sample image (differentiable: the backward's
+    # depth specialisations, gs_frame_backward_depth)
+    depth_acc = torch.zeros(S, H, W, device=dev) if spec.return_depth else None
+    m = spec.min_rgb_level / 255.0
+    prealloc = frame = None
+    if backend is None:
+        # the backward's frame-sized buffers (and the one fill among them) are issued BEFORE the frame: behind the
+        # frame's last read-back nothing but the averaging and the backward's own launches are left for the host
+        if want and GRAD_POOL and not pixvel:
+            # pooled gradient buffers (see _grad_pool): the entry is taken here, ahead of the frame like every other
+            # buffer of the backward; its persistent touched flags are all zero, and the projection backward stores
+            # the view-matrix gradients — no fill at all.  An entry whose backward never runs is never committed.
+            entry = _grad_pool_acquire(dev, N, P, K, sh_rest is not None)
+            prealloc = {"entry": entry, "touched": entry.touched, "v_records": torch.empty(P * N, GRAD, device=dev),
+                        "pose_scratch": _pose_scratch(N, P, True, dev)}
+        elif want:
+            # ONE zero fill for what this frame's backward accumulates into: touched flags [P*N] u8 | 16 P + 12 floats
+            # of view-matrix / twist gradients
+            t_len = (P * N + 15) // 16 * 16
+            zbuf = torch.zeros(t_len + 4 * (16 * P + 12), dtype=torch.uint8, device=dev)
+            zf = zbuf[t_len:].view(torch.float32)
+            prealloc = {"touched": zbuf[:P * N], "v_records": torch.empty(P * N, GRAD, device=dev), "v_V": zf[:16 * P],
+                        "v_tw": zf[16 * P:16 * P + 12], "pose_scratch": _pose_scratch(N, P, True, dev)}
+        # fused sub-frame averaging: the library launches it behind the last compositor
+        averaged = None
+        if spec.gamma is not None:
+            averaged = (spec.gamma, m, torch.empty((H, W, 3) if B == 1 else (B, H, W, 3), device=dev))
+        retries = 0
+        for attempt in range(_ARENA_ATTEMPTS):
+            try:
+                out_img, out_T, frame = native_frame_forward(records, dkeys, ntiles, P, N, S, R, H, W, bg, edges,
+                                                             hints.slice_base(), color, depth_acc, bool(want), rs,
+                                                             averaged, hints, bool(defer_flags & 4), lazy, cameras=B)
+                st = frame["state"]
+                hints.feedback(int(st.n_slices), retries, _box_share(st), int(st.depth_select),
+                               float(st.open_after_first), int(st.max_selected), int(st.select_overflow))
+                break
+            except _ArenaTooSmall:
+                retries += 1
+                if attempt == _ARENA_ATTEMPTS - 1:
+                    raise _lib.HipLibraryError("frame_forward: the arena estimate did not converge")
+                # the depth keys were consumed by the pre-sort: project again, then retry with the larger arena
+                if depth_acc is not None:
+                    depth_acc.zero_()
+                with _stage("project_fwd"):
+                    _project()
+        slices = []
+    else:
+        prealloc = {} if want else None
+        out_img, out_T, slices = backend.sliced_forward(records, dkeys, ntiles, P, N, S, R, H, W, bg, edges, SLICE_BASE,
+                                                        color, depth_acc, prealloc, rs)
+    first, samples, rgb = out_img, None, None
+    if spec.gamma is not None:
+        # fused sub-frame averaging: output 0 is the averaged image; backward never materialises the
+        # per-sample gradients (the compositor's backward derives them per pixel)
+        samples = out_img
+        if backend is None:
+            first = rgb = averaged[2]
+        else:
+            first = rgb = torch.empty(H, W, 3, device=dev)
+            with _stage("combine"):
+                _check(L.gs_combine_fwd(S, H * W * 3, _ptr(out_img), spec.gamma, m, _ptr(first), _stream()),
+                       "combine_fwd")
+    state = FrameSaved(spec, N, P, K, want, background is not None and "background" in want, frame, backend, slices,
+                       prealloc, rs, xy_grad_out, xy_absgrad_out)
+    tensors = FrameTensors(means, scales, quats, opacities, sh, sh_rest, V, twist, times, records, edges, bg, out_T,
+                           samples, rgb)
+    return (first, (1.0 - out_T) if spec.return_alpha else None, radii, depth_acc), state, tensors
+
+
+def frame_backward(state: FrameSaved, tensors: FrameTensors, v_img, v_alpha, v_depth=None) -> FrameGrads:
+    """state, tensors: what frame_forward returned; v_*: d loss / d (image, alphas, depth_acc) of its outputs (None: not
+    used by the loss) -> the gradients by name; the ones nobody asked for (state.want) or the frame has no
+    input for are None"""
+    if v_img is None and v_alpha is None and v_depth is None:
+        return FrameGrads()
+    spec, N, P, K = state.spec, state.N, state.P, state.K
+    S, R, H, W, B = spec.S, spec.R, spec.H, spec.W, spec.cameras
+    (means, scales, quats, opacities, sh, sh_rest, V, twist, times, records, edges, bg, out_T, samples,
+     rgb) = tensors
+    dev = means.device
+    L = _L()
+    if v_depth is not None:
+        # d loss / d depth_acc [S,H,W]: the depth specialisations of the native frame backward (grad flag 64 below)
+        if state.frame is None:
+            raise NotImplementedError("a depth gradient needs the native frame backward (gs_frame_backward_depth); "
+                                      "the frame backend in use has no depth channel")
+        v_depth = v_depth.contiguous().float()
+    if v_img is None:
+        v_img = torch.zeros((S, H, W, 3) if spec.gamma is None else ((H, W, 3) if B == 1 else (B, H, W, 3)), device=dev)
+    else:
+        v_img = v_img.contiguous().float()
+    v_al = None if v_alpha is None else v_alpha.contiguous().float()
+    combine = None
+    if spec.gamma is not None:
+        gamma, m = spec.gamma, spec.min_rgb_level / 255.0
+        # one camera, or B cameras of S / B samples each
+        bwd, bwd_scale, dims, tag = ((L.gs_combine_bwd_batched, L.gs_combine_bwd_scale_batched,
+                                      (B, S // B, rgb.numel() // B), "_batched") if B > 1 else
+                                     (L.gs_combine_bwd, L.gs_combine_bwd_scale, (S, rgb.numel()), ""))
+        if state.bg_grad:
+            # a learnable background needs the per-sample gradients themselves: two-step backward
+            v_samples = torch.empty_like(samples)
+            _check(bwd(*dims, _ptr(samples), gamma, m, _ptr(rgb), _ptr(v_img), _ptr(v_samples), _stream()),
+                   "combine_bwd" + tag)
+            v_img = v_samples
+        else:
+            scale = torch.empty_like(rgb)
+            with _stage("combine"):
+                _check(bwd_scale(*dims, gamma, _ptr(rgb), _ptr(v_img), _ptr(scale), _stream()),
+                       "combine_bwd_scale" + tag)
+            combine = (scale, gamma, m)
+            v_img = samples
+    # atomic-free path: only Gaussians the compositor touched get a gradient record (plain stores) and a
+    # `touched` flag; the projection backward skips everything else, so v_records needs no 240 MB memset
+    all_tuples = state.frame is not None or all(sl["gi_of_e"] is not None for sl in state.slices)
+    pre = state.prealloc if state.prealloc else {}
+    state.prealloc = None
+    entry = None
+    if all_tuples and pre.get("entry") is not None and state.frame is not None:
+        entry = pre["entry"]
+        v_records, touched = pre["v_records"], entry.touched
+    elif all_tuples and "touched" in pre:
+        v_records, touched = pre["v_records"], pre["touched"]
+    elif all_tuples:
+        v_records = torch.empty(P * N, GRAD, device=dev)
+        touched = torch.zeros(P * N, dtype=torch.uint8, device=dev)
+    else:
+        v_records = torch.zeros(P * N, GRAD, device=dev)
+        touched = None
+
+    xy_abs = state.xy_absgrad_out
+    if state.frame is not None:
+        native_frame_backward(state.frame, records, bg, edges, out_T, v_img, v_al, v_records, touched, combine, v_depth,
+                              xy_abs is not None)
+        if xy_abs is not None:
+            # camera b's ordered sum over its sub-poses of v_records[:, 9:11], touched rows only; every row stored
+            _check(L.gs_xy_absgrad_sum(N, P, B, _ptr(v_records), _ptr(touched), _ptr(xy_abs), _stream()),
+                   "xy_absgrad_sum")
+    else:
+        state.backend.sliced_backward(records, state.slices, S, R, H, W, bg, edges, out_T, v_img, v_al, v_records,
+                                      touched, combine, state.rs)
+    # the dense gradient outputs are carved out of ONE buffer; with touched flags the projection backward zero-fills
+    # its own outputs (grad flag 32): no fill launches (round 3: one 236 MB fill per step)
+    sizes = [3 * N, 3 * N, 4 * N, N] + ([3 * K * N] if sh_rest is None else [3 * N, 3 * (K - 1) * N])
+    shapes = [(N, 3), (N, 3), (N, 4), (N,)] + ([(N, K, 3)] if sh_rest is None else [tuple(sh.shape), (N, K - 1, 3)])
+    flat = torch.empty(sum(sizes), device=dev) if entry is None else entry.flat
+    outs = [t.view(shape) for t, shape in zip(flat.split(sizes), shapes)]
+    v_means, v_scales, v_quats, v_opac, v_sh = outs[:5]
+    v_sh_rest = outs[5] if sh_rest is not None else None
+    need_v, need_tw = "viewmats" in state.want, "twist" in state.want
+    xy_out = state.xy_grad_out
+    fill_flag = (32 if touched is not None else 0) | (64 if v_depth is not None else 0)     # 64: v_records[:, 11]
+    # 128 | B << 8: xy_grad_out is [B,N,2], one row per camera (a batch always has touched flags)
+    xy_cams = (128 | (B << 8)) if (B > 1 and xy_out is not None) else 0
+    v_lin = v_ang = None
+    # scratch of the ordered camera-gradient reduction (the sparse form runs when touched flags exist)
+    psc = pre.get("pose_scratch") if touched is not None else None
+    if psc is None and (need_v or need_tw):
+        psc = _pose_scratch(N, P, touched is not None, dev)
+    # what the three projection backwards share: the inputs up to the view matrices, the intrinsics up to d loss / d sh,
+    # and the raw-parameter tail
+    head = (N, P, _ptr(means), _ptr(scales), spec.glob_scale, _ptr(quats), _ptr(opacities), _ptr(sh), K, spec.sh_degree,
+            _ptr(V))
+    mid = (spec.fx, spec.fy, spec.cx, spec.cy, H, W, spec.clip_thresh, spec.antialiased, _ptr(records), _ptr(v_records),
+           _ptr(v_means), _ptr(v_scales), _ptr(v_quats), _ptr(v_opac), _ptr(v_sh))
+    tail = (_ptr(sh_rest), spec.param_flags, _ptr(v_sh_rest), _ptr(psc), 0 if psc is None else psc.numel(), _stream())
+    with _stage("project_bwd"):
+        if twist is not None:
+            v_V = (pre["v_V"][:16].view(4, 4) if "v_V" in pre else torch.zeros(4, 4, device=dev)) if need_v else None
+            v_tw = (pre["v_tw"] if "v_tw" in pre else torch.zeros(12, device=dev)) if need_tw else None
+            _check(L.gs_project_pixvel_bwd(*head, _ptr(twist), _ptr(times), *mid, _ptr(v_V), _ptr(v_tw), _ptr(touched),
+                                           _ptr(xy_out),
+                                           _proj_grad_flags() | (16 if state.rs is not None else 0) | fill_flag, *tail),
+                   "project_pixvel_bwd")
+            if v_tw is not None:
+                v_lin, v_ang = v_tw[0:3], v_tw[3:6]
+        elif entry is not None:
+            # pooled: only the rows the entry's last step dirtied are zeroed; v_V is stored, not accumulated into
+            v_V = torch.empty(P, 4, 4, device=dev) if need_v else None
+            _check(L.gs_project_fused_bwd_pooled(*head, *mid, _ptr(v_V), _ptr(touched), _ptr(xy_out),
+                                                 _proj_grad_flags() | fill_flag | xy_cams, *tail, _ptr(entry.dirty)),
+                   "project_fused_bwd_pooled")
+            _grad_pool_commit(entry)
+        else:
+            v_V = (pre["v_V"].view(P, 4, 4) if "v_V" in pre else torch.zeros(P, 4, 4, device=dev)) if need_v else None
+            _check(L.gs_project_fused_bwd(*head, *mid, _ptr(v_V), _ptr(touched), _ptr(xy_out),
+                                          _proj_grad_flags() | fill_flag | xy_cams, *tail), "project_fused_bwd")
+    v_bg = (out_T[..., None] * v_img).sum(dim=(0, 1, 2)) if state.bg_grad else None
+    return FrameGrads(v_means, v_scales, v_quats, v_opac, v_sh, v_sh_rest, v_V, v_bg, v_lin, v_ang)
+
+
+# the inputs of the autograd node: the spec, the FrameExtras, then the tensors that can carry a gradient
+_FRAME_NODE_INPUTS = ("spec", "extras") + FRAME_TENSORS
+
+
 class _RenderSubposes(Function):
     @staticmethod
-    def forward(ctx, means3d, scales, quats, opacities, sh, viewmats, background, S, R, fx, fy, cx, cy,
-                img_height, img_width, sh_degree, antialiased, glob_scale, clip_thresh, xy_grad_out, return_alpha,
-                gamma, min_rgb_level, lin_vel=None, ang_vel=None, times=None, return_depth=False, rs_time=0.0,
-                sh_rest=None, param_flags=0, shared_list=False, hints=None, cameras=1, xy_absgrad_out=None):
+    def forward(ctx, spec, extras, *tensors):
         # an output the loss does not use arrives as None in backward instead of a materialised zero tensor
         ctx.set_materialize_grads(False)
-        if xy_absgrad_out is not None:
-            # refused before any device work: the pixel-velocity compositor keeps d loss / d pixel velocity in the tuple
-            # slots absgrad uses, and a test frame backend has no absgrad compositor
-            if times is not None:
-                raise ValueError("xy_absgrad_out is not available with the pixel-velocity model (times=): its backward "
-                                 "compositor uses gradient slots 9 and 10 for d loss / d pixel velocity")
-            if frame_backend is not None and not frame_backend.native_ok():
-                raise ValueError("xy_absgrad_out needs the library's frame path (the absgrad backward compositors); the "
-                                 "frame backend in use has none")
-        means3d, scales, quats = _f32(means3d, "means3d"), _f32(scales, "scales"), _f32(quats, "quats")
-        opacities, sh = _f32(opacities, "opacities").reshape(-1), _f32(sh, "sh")
-        # raw splatfacto parameters (param_flags bit 0: log-scales, bit 1: opacity logits; sh_rest: features_rest beside
-        # sh = features_dc): activations, their backward and the SH concatenation happen inside the projection kernels
-        param_flags = int(param_flags)
-        if sh_rest is not None:
-            sh_rest = _f32(sh_rest, "sh_rest")
-            if sh.reshape(sh.shape[0], -1).shape[1] != 3 or sh_rest.dim() != 3 or sh_rest.shape[0] != sh.shape[0]:
-                raise ValueError("with sh_rest [N,K-1,3], sh must be features_dc [N,3] (or [N,1,3])")
-        # B > 1 cameras in one frame (render_batch): S and the viewmats span all of them, camera b owns sample images
-        # [b*S/B, (b+1)*S/B) and sub-poses [b*P/B, (b+1)*P/B)
-        B = max(1, int(cameras))
-        xy_shape = (means3d.shape[0], 2) if B == 1 else (B, means3d.shape[0], 2)
-        if xy_grad_out is not None:
-            if (xy_grad_out.shape != xy_shape or xy_grad_out.dtype != torch.float32
-                    or not xy_grad_out.is_contiguous() or xy_grad_out.device != means3d.device):
-                raise ValueError(f"xy_grad_out must be a contiguous float32 {list(xy_shape)} tensor on the Gaussians' "
-                                 f"device")
-        ctx.xy_grad_out = xy_grad_out
-        if xy_absgrad_out is not None:
-            if (xy_absgrad_out.shape != xy_shape or xy_absgrad_out.dtype != torch.float32
-                    or not xy_absgrad_out.is_contiguous() or xy_absgrad_out.device != means3d.device):
-                raise ValueError(f"xy_absgrad_out must be a contiguous float32 {list(xy_shape)} tensor on the Gaussians' "
-                                 f"device")
-        ctx.xy_absgrad_out = xy_absgrad_out
-        N, K = means3d.shape[0], (sh.shape[1] if sh_rest is None else 1 + sh_rest.shape[1])
-        P = S * R
-        if P > MAX_SUBPOSES:
-            raise ValueError(f"{S} blur samples x {R} row bands = {P} sub-poses per frame; the slice descriptors travel "
-                             f"in kernel arguments and hold at most {MAX_SUBPOSES} (kMaxSubposes, csrc/binning.hip)")
-        # pixel-velocity model: ONE mid-exposure viewmat + the camera twist + the P sub-pose times
-        pixvel = times is not None
-        rs_time = float(rs_time or 0.0)
-        if rs_time != 0.0 and (not pixvel or R != 1):
-            raise ValueError("exact rolling shutter (rolling_shutter_time != 0) needs the pixel-velocity model "
-                             "(times / lin_vel / ang_vel) and rs_bands == 1")
-        # shared list (pixel-velocity model, rs_bands == 1): ONE record set, depth sort and tile list for the frame —
-        # the splats at the centre of the sampled time span, tile boxes swept over the whole span (+ readout); the
-        # compositor evaluates sample s at xy + (times[s] - centre + tau(y)) * pixel_velocity
-        shared = None
-        if shared_list:
-            if not pixvel or R != 1:
-                raise ValueError("shared_list needs the pixel-velocity model (times / lin_vel / ang_vel) and rs_bands == 1")
-            tl = [float(t) for t in (times.reshape(-1).tolist() if isinstance(times, Tensor) else times)]
-            if len(tl) != S:
-                raise ValueError(f"times must hold {S} sample times")
-            t_c = 0.5 * (min(tl) + max(tl))
-            shared = (torch.tensor([t - t_c for t in tl], dtype=torch.float32, device=means3d.device),
-                      (max(tl) - min(tl)) + abs(rs_time), (min(tl) - t_c, max(tl) - t_c))
-            times = torch.tensor([t_c], dtype=torch.float32, device=means3d.device)
-            P = 1
-        if pixvel:
-            V = _viewmat16(viewmats).reshape(4, 4)
-            twist = torch.cat([_f32(lin_vel, "lin_vel").reshape(3), _f32(ang_vel, "ang_vel").reshape(3)]).contiguous()
-            times = _f32(times, "times").reshape(-1)
-            if times.numel() != P:
-                raise ValueError(f"times must hold {P} sub-pose times")
-        else:
-            V = _f32(viewmats, "viewmats")
-            twist = None
-            if V.shape != (P, 4, 4):
-                raise ValueError(f"viewmats must be [{P},4,4]")
-        H, W = int(img_height), int(img_width)
-        dev = means3d.device
-        L = _L()
-        records = torch.empty(P * N, REC, device=dev)
-        dkeys = torch.empty(P * N, dtype=torch.int32, device=dev)
-        ntiles = torch.empty(P * N, dtype=torch.int32, device=dev)
-        radii = torch.empty(P, N, dtype=torch.int32, device=dev)
-        args = (N, P, float(glob_scale), K, int(sh_degree), float(fx), float(fy), float(cx), float(cy), H, W,
-                float(clip_thresh), int(bool(antialiased)))
-        # bit 1: culled (Gaussian, sub-pose) pairs get no record at all.  Safe when nothing downstream looks at them:
-        # the compacting pre-sort never ranks them and the tuple backward only visits rows the compositor touched
-        # (the atomics backward of the pixel-velocity model tells "covers no tile" by an all-zero record)
-        # bit 0: SH colour deferred to the depth slices (gs_slice_colors colours only what a slice emits)
-        backend = frame_backend if (frame_backend is not None and not frame_backend.native_ok()) else None
-        defer_flags = 3 if backend is None else backend.defer_flags()
-        # bit 2 + R in bits 8..23: band-aware projection (a (band, Gaussian) pair whose tile rows miss the band is culled
-        # before the depth pre-sort instead of being keyed, sorted, scanned and planned for nothing)
-        if backend is None and R > 1 and BAND_AWARE:
-            defer_flags |= 4 | (R << 8)
-        if B > 1 and (pixvel or shared is not None or backend is not None):
-            raise NotImplementedError("a frame of several cameras renders SE(3) sub-poses through the library's frame "
-                                      "path (no pixel-velocity model, shared list or frame backend)")
-        if backend is None and hints is None:
-            # default owner of the frame-to-frame hints: the scene's shape AND its parameter storage, so that two
-            # scenes of one shape do not share a budget / arena estimate (and the camera count of a batch)
-            key = (str(dev), N, P, S, H, W, shared is not None, means3d.untyped_storage().data_ptr())
-            hints = hints_for(key if B == 1 else key + (B,))
-        # lazy records (see LAZY_RECORDS): SE(3) sub-poses through the library's frame path, planned slices, and a scene
-        # whose frames have so far stopped within the default budget
-        lazy = None
-        if (backend is None and not pixvel and LAZY_RECORDS and hints.slice_base() > 0
-                and (LAZY_RECORDS == 2 or hints.lazy_records())):
-            defer_flags |= 16
-        if shared is not None and backend is not None:
-            raise ValueError("the shared-list mode runs through the library's frame path only")
-        pix_vel = torch.empty(N, 2, device=dev) if (rs_time != 0.0 or shared is not None) else None
-        rs = None if pix_vel is None else (pix_vel, rs_time) + ((shared[0], shared[2]) if shared is not None else ())
-        box_sweep = shared[1] if shared is not None else rs_time      # what the projection widens the tile boxes by
-        ctx.rs = rs
-
-        def _project():
-            if pixvel:
-                _check(L.gs_project_pixvel_fwd(N, P, _ptr(means3d), _ptr(scales), args[2], _ptr(quats), _ptr(opacities),
-                                               _ptr(sh), K, args[4], _ptr(V), _ptr(twist), _ptr(times), args[5], args[6],
-                                               args[7], args[8], H, W, args[11], args[12], defer_flags,
-                                               _ptr(records), _ptr(dkeys), _ptr(ntiles), _ptr(radii), box_sweep,
-                                               _ptr(pix_vel), _ptr(sh_rest), param_flags, _stream()),
-                       "project_pixvel_fwd")
-            else:
-                _check(L.gs_project_fused_fwd(N, P, _ptr(means3d), _ptr(scales), args[2], _ptr(quats), _ptr(opacities),
-                                              _ptr(sh), K, args[4], _ptr(V), args[5], args[6], args[7], args[8], H, W,
-                                              args[11], args[12], defer_flags, _ptr(records), _ptr(dkeys),
-                                              _ptr(ntiles), _ptr(radii), _ptr(sh_rest), param_flags, _stream()),
-                       "project_fused_fwd")
-
-        with _stage("project_fwd"):
-            _project()
-        if defer_flags & 16:
-            lazy = _ProjectInputs(means3d.data_ptr(), scales.data_ptr(), quats.data_ptr(), opacities.data_ptr(),
-                                  V.data_ptr(), args[2], args[5], args[6], args[7], args[8], args[11], args[12],
-                                  defer_flags & ~16, param_flags)
-        bg = _background(background, dev)
-        edges = _band_edges(H, R, dev)
-        # deferred colour: the view direction of every sub-pose (pixel-velocity model: the mid-exposure pose for all)
-        V_col = V.reshape(1, 16).expand(P, 16).contiguous() if pixvel else V
-        color = (means3d, sh, sh_rest, K, args[4], V_col) if (defer_flags & 1) else None
-        # optional fourth channel: sum of weight * camera-space depth per sample image (differentiable: the backward's
-        # depth specialisations, gs_frame_backward_depth)
-        depth_acc = torch.zeros(S, H, W, device=dev) if return_depth else None
-        ctx.prealloc = None
-        ctx.frame = None
-        ctx.backend = backend
-        if backend is None:
-            if rs is not None and R != 1:
-                raise ValueError("exact rolling shutter renders with rs_bands == 1")
-            # the backward's frame-sized buffers (and the one fill among them) are issued BEFORE the frame: behind the
-            # frame's last read-back nothing but the averaging and the backward's own launches are left for the host
-            if any(ctx.needs_input_grad) and GRAD_POOL and not pixvel:
-                # pooled gradient buffers (see _grad_pool): the entry is taken here, ahead of the frame like every other
-                # buffer of the backward; its persistent touched flags are all zero, and the projection backward stores
-                # the view-matrix gradients — no fill at all.  An entry whose backward never runs is never committed.
-                entry = _grad_pool_acquire(dev, N, P, K, sh_rest is not None)
-                ctx.prealloc = {"entry": entry, "touched": entry.touched,
-                                "v_records": torch.empty(P * N, GRAD, device=dev),
-                                "pose_scratch": _pose_scratch(N, P, True, dev)}
-            elif any(ctx.needs_input_grad):
-                # ONE zero fill for what this node's backward accumulates into: touched flags [P*N] u8 | 16 P + 12 floats
-                # of view-matrix / twist gradients
-                t_len = (P * N + 15) // 16 * 16
-                zbuf = torch.zeros(t_len + 4 * (16 * P + 12), dtype=torch.uint8, device=dev)
-                zf = zbuf[t_len:].view(torch.float32)
-                ctx.prealloc = {"touched": zbuf[:P * N], "v_records": torch.empty(P * N, GRAD, device=dev),
-                                "v_V": zf[:16 * P], "v_tw": zf[16 * P:16 * P + 12],
-                                "pose_scratch": _pose_scratch(N, P, True, dev)}
-            # fused sub-frame averaging: the library launches it behind the last compositor (below: `averaged`)
-            averaged = None
-            if gamma is not None:
-                averaged = (float(gamma), float(min_rgb_level) / 255.0,
-                            torch.empty((H, W, 3) if B == 1 else (B, H, W, 3), device=dev))
-            retries = 0
-            for attempt in range(_ARENA_ATTEMPTS):
-                try:
-                    out_img, out_T, ctx.frame = native_frame_forward(records, dkeys, ntiles, P, N, S, R, H, W, bg, edges,
-                                                                     hints.slice_base(), color, depth_acc,
-                                                                     any(ctx.needs_input_grad), rs, averaged, hints,
-                                                                     bool(defer_flags & 4), lazy, cameras=B)
-                    hints.feedback(int(ctx.frame["state"].n_slices), retries, _box_share(ctx.frame["state"]),
-                                   int(ctx.frame["state"].depth_select), float(ctx.frame["state"].open_after_first),
-                                   int(ctx.frame["state"].max_selected), int(ctx.frame["state"].select_overflow))
-                    break
-                except _ArenaTooSmall:
-                    retries += 1
-                    if attempt == _ARENA_ATTEMPTS - 1:
-                        raise _lib.HipLibraryError("frame_forward: the arena estimate did not converge")
-                    # the depth keys were consumed by the pre-sort: project again, then retry with the larger arena
-                    if depth_acc is not None:
-                        depth_acc.zero_()
-                    with _stage("project_fwd"):
-                        _project()
-            slices = []
-        else:
-            ctx.prealloc = {} if any(ctx.needs_input_grad) else None
-            out_img, out_T, slices = backend.sliced_forward(records, dkeys, ntiles, P, N, S, R, H, W, bg, edges, SLICE_BASE,
-                                                            color, depth_acc, ctx.prealloc, rs)
-        ctx.slices = slices
-        svals = bins = fidx = _placeholder_i32(dev)       # nothing to keep: the slices hold their own lists
-        n_isect = last_num_intersects
-        ctx.combine = None
-        first = cmb_samples = cmb_rgb = out_img
-        if gamma is not None:
-            # fused sub-frame averaging: output 0 is the averaged image; backward never materialises the
-            # per-sample gradients (the compositor's backward derives them per pixel)
-            m = float(min_rgb_level) / 255.0
-            if backend is None:
-                first = cmb_rgb = averaged[2]
-            else:
-                first = cmb_rgb = torch.empty(H, W, 3, device=dev)
-                with _stage("combine"):
-                    _check(L.gs_combine_fwd(S, H * W * 3, _ptr(out_img), float(gamma), m, _ptr(first), _stream()),
-                           "combine_fwd")
-            ctx.combine = (float(gamma), m)
-        else:
-            cmb_samples = cmb_rgb = svals          # placeholders: nothing to keep
-        ctx.pixvel = (twist, times) if pixvel else None
-        ctx.param_flags = param_flags
-        ctx.sh_rest = sh_rest
-        ctx.save_for_backward(means3d, scales, quats, opacities, sh, V, records, svals, bins, edges, bg, out_T, fidx,
-                              cmb_samples, cmb_rgb)
-        ctx.args = args
-        ctx.SR = (S, R)
-        ctx.n_isect = n_isect
-        ctx.bg_grad = background is not None and ctx.needs_input_grad[6]
+        want = frozenset(_WANT_OF[name] for name, need in zip(_FRAME_NODE_INPUTS, ctx.needs_input_grad)
+                         if need and name in _WANT_OF)
+        outs, ctx.state, saved = frame_forward(spec, **dict(zip(FRAME_TENSORS, tensors)), want=want, **extras._asdict())
+        # the tensors go through the node (its in-place-modification check, no reference cycle over the outputs)
+        ctx.save_for_backward(*saved)
+        _, _, radii, _ = outs
         ctx.mark_non_differentiable(radii)
-        ctx.img_shape = (S, H, W, 3) if gamma is None else ((H, W, 3) if B == 1 else (B, H, W, 3))
-        ctx.cameras = B
-        return first, (1.0 - out_T) if return_alpha else None, radii, depth_acc
+        return outs
 
     @staticmethod
     def backward(ctx, v_img, v_alpha, _v_radii, v_depth=None):
-        (means3d, scales, quats, opacities, sh, V, records, svals, bins, edges, bg, out_T, fidx, cmb_samples,
-         cmb_rgb) = ctx.saved_tensors
-        N, P, glob, K, deg, fx, fy, cx, cy, H, W, clip, aa = ctx.args
-        S, R = ctx.SR
-        dev = means3d.device
-        L = _L()
-        if v_img is None and v_alpha is None and v_depth is None:
-            return (None,) * 34
-        B = ctx.cameras
-        if v_depth is not None:
-            # d loss / d depth_acc [S,H,W]: the depth specialisations of the native frame backward (grad flag 64 below)
-            if ctx.frame is None:
-                raise NotImplementedError("a depth gradient needs the native frame backward (gs_frame_backward_depth); "
-                                          "the frame backend in use has no depth channel")
-            v_depth = v_depth.contiguous().float()
-        v_img = torch.zeros(ctx.img_shape, device=dev) if v_img is None else v_img.contiguous().float()
-        v_al = None if v_alpha is None else v_alpha.contiguous().float()
-        combine = None
-        if ctx.combine is not None:
-            samples, rgb = cmb_samples, cmb_rgb
-            gamma, m = ctx.combine
-            if ctx.bg_grad:
-                # a learnable background needs the per-sample gradients themselves: two-step backward
-                v_samples = torch.empty_like(samples)
-                if B > 1:
-                    _check(L.gs_combine_bwd_batched(B, S // B, rgb.numel() // B, _ptr(samples), gamma, m, _ptr(rgb),
-                                                    _ptr(v_img), _ptr(v_samples), _stream()), "combine_bwd_batched")
-                else:
-                    _check(L.gs_combine_bwd(S, rgb.numel(), _ptr(samples), gamma, m, _ptr(rgb), _ptr(v_img),
-                                            _ptr(v_samples), _stream()), "combine_bwd")
-                v_img = v_samples
-            else:
-                scale = torch.empty_like(rgb)
-                with _stage("combine"):
-                    if B > 1:
-                        _check(L.gs_combine_bwd_scale_batched(B, S // B, rgb.numel() // B, gamma, _ptr(rgb), _ptr(v_img),
-                                                              _ptr(scale), _stream()), "combine_bwd_scale_batched")
-                    else:
-                        _check(L.gs_combine_bwd_scale(S, rgb.numel(), gamma, _ptr(rgb), _ptr(v_img), _ptr(scale),
-                                                      _stream()), "combine_bwd_scale")
-                combine = (scale, gamma, m)
-                v_img = samples
-        # atomic-free path: only Gaussians the compositor touched get a gradient record (plain stores) and a
-        # `touched` flag; the projection backward skips everything else, so v_records needs no 240 MB memset
-        all_tuples = ctx.frame is not None or all(sl["gi_of_e"] is not None for sl in ctx.slices)
-        pre = ctx.prealloc if ctx.prealloc else {}
-        ctx.prealloc = None
-        entry = None
-        if all_tuples and pre.get("entry") is not None and ctx.frame is not None:
-            entry = pre["entry"]
-            v_records, touched = pre["v_records"], entry.touched
-        elif all_tuples and "touched" in pre:
-            v_records, touched = pre["v_records"], pre["touched"]
-        elif all_tuples:
-            v_records = torch.empty(P * N, GRAD, device=dev)
-            touched = torch.zeros(P * N, dtype=torch.uint8, device=dev)
-        else:
-            v_records = torch.zeros(P * N, GRAD, device=dev)
-            touched = None
+        grads = frame_backward(ctx.state, FrameTensors._make(ctx.saved_tensors), v_img, v_alpha, v_depth)
+        return tuple(getattr(grads, name, None) for name in _FRAME_NODE_INPUTS)
 
-        if ctx.frame is not None:
-            native_frame_backward(ctx.frame, records, bg, edges, out_T, v_img, v_al, v_records, touched, combine, v_depth,
-                                  ctx.xy_absgrad_out is not None)
-            if ctx.xy_absgrad_out is not None:
-                # camera b's ordered sum over its sub-poses of v_records[:, 9:11], touched rows only; every row stored
-                _check(L.gs_xy_absgrad_sum(N, P, B, _ptr(v_records), _ptr(touched), _ptr(ctx.xy_absgrad_out), _stream()),
-                       "xy_absgrad_sum")
-        else:
-            ctx.backend.sliced_backward(records, ctx.slices, S, R, H, W, bg, edges, out_T, v_img, v_al, v_records, touched,
-                                        combine, ctx.rs)
-        # the dense gradient outputs are carved out of ONE buffer; with touched flags the projection backward zero-fills
-        # its own outputs (grad flag 32): no fill launches (round 3: one 236 MB fill per step)
-        sh_rest = ctx.sh_rest
-        sizes = [3 * N, 3 * N, 4 * N, N] + ([3 * K * N] if sh_rest is None else [3 * N, 3 * (K - 1) * N])
-        shapes = [(N, 3), (N, 3), (N, 4), (N,)] + ([(N, K, 3)] if sh_rest is None else [tuple(sh.shape), (N, K - 1, 3)])
-        flat = torch.empty(sum(sizes), device=dev) if entry is None else entry.flat
-        outs = [t.view(shape) for t, shape in zip(flat.split(sizes), shapes)]
-        v_means, v_scales, v_quats, v_opac, v_sh = outs[:5]
-        v_sh_rest = outs[5] if sh_rest is not None else None
-        need_v = ctx.needs_input_grad[5]
-        xy_out = ctx.xy_grad_out
-        fill_flag = (32 if touched is not None else 0) | (64 if v_depth is not None else 0)     # 64: v_records[:, 11]
-        # 128 | B << 8: xy_grad_out is [B,N,2], one row per camera (a batch always has touched flags)
-        xy_cams = (128 | (B << 8)) if (B > 1 and xy_out is not None) else 0
-        pf = ctx.param_flags
-        v_lin = v_ang = None
-        # scratch of the ordered camera-gradient reduction (the sparse form runs when touched flags exist)
-        psc = pre.get("pose_scratch") if touched is not None else None
-        if psc is None and (need_v or ctx.needs_input_grad[23] or ctx.needs_input_grad[24]):
-            psc = _pose_scratch(N, P, touched is not None, dev)
-        psc_n = 0 if psc is None else psc.numel()
-        with _stage("project_bwd"):
-            if ctx.pixvel is not None:
-                twist, times = ctx.pixvel
-                v_V = (pre["v_V"][:16].view(4, 4) if "v_V" in pre else torch.zeros(4, 4, device=dev)) if need_v else None
-                need_tw = ctx.needs_input_grad[23] or ctx.needs_input_grad[24]
-                v_tw = (pre["v_tw"] if "v_tw" in pre else torch.zeros(12, device=dev)) if need_tw else None
-                _check(L.gs_project_pixvel_bwd(N, P, _ptr(means3d), _ptr(scales), glob, _ptr(quats), _ptr(opacities),
-                                               _ptr(sh), K, deg, _ptr(V), _ptr(twist), _ptr(times), fx, fy, cx, cy, H, W,
-                                               clip, aa, _ptr(records), _ptr(v_records), _ptr(v_means), _ptr(v_scales),
-                                               _ptr(v_quats), _ptr(v_opac), _ptr(v_sh), _ptr(v_V), _ptr(v_tw),
-                                               _ptr(touched), _ptr(xy_out),
-                                               _proj_grad_flags() | (16 if ctx.rs is not None else 0) | fill_flag,
-                                               _ptr(sh_rest), pf, _ptr(v_sh_rest), _ptr(psc), psc_n, _stream()),
-                       "project_pixvel_bwd")
-                if v_tw is not None:
-                    v_lin, v_ang = v_tw[0:3], v_tw[3:6]
-            elif entry is not None:
-                # pooled: only the rows the entry's last step dirtied are zeroed; v_V is stored, not accumulated into
-                v_V = torch.empty(P, 4, 4, device=dev) if need_v else None
-                _check(L.gs_project_fused_bwd_pooled(N, P, _ptr(means3d), _ptr(scales), glob, _ptr(quats),
-                                                     _ptr(opacities), _ptr(sh), K, deg, _ptr(V), fx, fy, cx, cy, H, W,
-                                                     clip, aa, _ptr(records), _ptr(v_records), _ptr(v_means),
-                                                     _ptr(v_scales), _ptr(v_quats), _ptr(v_opac), _ptr(v_sh), _ptr(v_V),
-                                                     _ptr(touched), _ptr(xy_out), _proj_grad_flags() | fill_flag | xy_cams,
-                                                     _ptr(sh_rest), pf, _ptr(v_sh_rest), _ptr(psc), psc_n, _stream(),
-                                                     _ptr(entry.dirty)), "project_fused_bwd_pooled")
-                _grad_pool_commit(entry)
-            else:
-                v_V = (pre["v_V"].view(P, 4, 4) if "v_V" in pre else torch.zeros(P, 4, 4, device=dev)) if need_v else None
-                _check(L.gs_project_fused_bwd(N, P, _ptr(means3d), _ptr(scales), glob, _ptr(quats), _ptr(opacities),
-                                              _ptr(sh), K, deg, _ptr(V), fx, fy, cx, cy, H, W, clip, aa, _ptr(records),
-                                              _ptr(v_records), _ptr(v_means), _ptr(v_scales), _ptr(v_quats),
-                                              _ptr(v_opac), _ptr(v_sh), _ptr(v_V), _ptr(touched), _ptr(xy_out),
-                                              _proj_grad_flags() | fill_flag | xy_cams, _ptr(sh_rest), pf, _ptr(v_sh_rest),
-                                              _ptr(psc), psc_n, _stream()), "project_fused_bwd")
-        v_bg = (out_T[..., None] * v_img).sum(dim=(0, 1, 2)) if ctx.bg_grad else None
-        return ((v_means, v_scales, v_quats, v_opac, v_sh, v_V, v_bg) + (None,) * 16
-                + (v_lin, v_ang, None, None, None, v_sh_rest, None, None, None, None, None))
+
+def _render_frame(spec: FrameSpec, extras: FrameExtras, **tensors):
+    """the one call the public entry points make: -> (image, alphas or None, radii, depth_acc or None)"""
+    return _RenderSubposes.apply(spec, extras, *(tensors.get(name) for name in FRAME_TENSORS))
 
 
 def render_subposes(means3d: Tensor, scales: Tensor, quats: Tensor, opacities: Tensor, sh: Tensor,
@@ -1744,12 +1815,13 @@ def render_subposes(means3d: Tensor, scales: Tensor, quats: Tensor, opacities: T
     by that fringe.
     hints: the caller's FrameHints (adaptive slice budget + arena estimate of ITS scene); None = one per (device, frame
     shape, storage of means3d)."""
-    S, R = max(1, int(blur_samples)), max(1, int(rs_bands))
-    out = _RenderSubposes.apply(means3d, scales, quats, opacities, sh, viewmats, background, S, R, fx, fy, cx, cy,
-                                img_height, img_width, sh_degree, antialiased, glob_scale, clip_thresh, xy_grad_out,
-                                bool(return_alpha), None, None, lin_vel, ang_vel, times, bool(return_depth),
-                                float(rolling_shutter_time), sh_rest, 3 if raw_params else 0,
-                                bool(shared_list), hints, 1, xy_absgrad_out)
+    spec = FrameSpec.of(max(1, int(blur_samples)), max(1, int(rs_bands)), fx, fy, cx, cy, img_height, img_width,
+                        sh_degree=sh_degree, antialiased=antialiased, glob_scale=glob_scale, clip_thresh=clip_thresh,
+                        return_alpha=return_alpha, return_depth=return_depth, rs_time=rolling_shutter_time,
+                        raw_params=raw_params, shared_list=shared_list)
+    out = _render_frame(spec, FrameExtras(times, xy_grad_out, xy_absgrad_out, hints), means=means3d, scales=scales,
+                        quats=quats, opacities=opacities, sh=sh, sh_rest=sh_rest, viewmats=viewmats,
+                        background=background, lin_vel=lin_vel, ang_vel=ang_vel)
     return out if return_depth else out[:3]
 
 
@@ -1766,12 +1838,13 @@ def render_combined(means3d: Tensor, scales: Tensor, quats: Tensor, opacities: T
     Same values as the two-step form; the backward skips the [S,H,W,3] per-sample gradient tensor — the
     compositor's backward derives every pixel's sample gradient from rgb and its gradient.
     xy_absgrad_out: as in render_subposes (float32 [N,2], OVERWRITTEN during backward with the absgrad statistic)."""
-    S, R = max(1, int(blur_samples)), max(1, int(rs_bands))
-    out = _RenderSubposes.apply(means3d, scales, quats, opacities, sh, viewmats, background, S, R, fx, fy, cx, cy,
-                                img_height, img_width, sh_degree, antialiased, glob_scale, clip_thresh, xy_grad_out,
-                                bool(return_alpha), float(gamma), float(min_rgb_level), lin_vel, ang_vel, times,
-                                bool(return_depth), float(rolling_shutter_time), sh_rest, 3 if raw_params else 0,
-                                bool(shared_list), hints, 1, xy_absgrad_out)
+    spec = FrameSpec.of(max(1, int(blur_samples)), max(1, int(rs_bands)), fx, fy, cx, cy, img_height, img_width,
+                        sh_degree=sh_degree, antialiased=antialiased, glob_scale=glob_scale, clip_thresh=clip_thresh,
+                        gamma=gamma, min_rgb_level=min_rgb_level, return_alpha=return_alpha, return_depth=return_depth,
+                        rs_time=rolling_shutter_time, raw_params=raw_params, shared_list=shared_list)
+    out = _render_frame(spec, FrameExtras(times, xy_grad_out, xy_absgrad_out, hints), means=means3d, scales=scales,
+                        quats=quats, opacities=opacities, sh=sh, sh_rest=sh_rest, viewmats=viewmats,
+                        background=background, lin_vel=lin_vel, ang_vel=ang_vel)
     return out if return_depth else out[:3]
 
 
@@ -1812,16 +1885,8 @@ def render_batch(means3d: Tensor, scales: Tensor, quats: Tensor, opacities: Tens
     (render_subposes), equal to that of camera b rendered alone.
     Limits: B*S*R <= MAX_SUBPOSES and B*S*H*W < 2^30 (check_batch).  The pixel-velocity model (times) and the shared
     list are single-camera forms (NotImplementedError), as is the Python frame backend.  B == 1 is render_combined."""
-    if times is not None and xy_absgrad_out is not None:
-        raise ValueError("xy_absgrad_out is not available with the pixel-velocity model (times=)")
-    if times is not None:
-        raise NotImplementedError("render_batch renders SE(3) sub-poses; the pixel-velocity model (times=) renders one "
-                                  "camera per call (render_combined)")
-    if shared_list:
-        raise NotImplementedError("render_batch has no shared-list mode (pixel-velocity model, one camera per call)")
-    if frame_backend is not None and not frame_backend.native_ok():
-        raise NotImplementedError("render_batch runs through the library's frame path only; the Python frame backend "
-                                  "renders one camera per call")
+    _validate_frame(pixvel=times is not None, R=1, rs_time=0.0, shared_list=bool(shared_list),
+                    absgrad=xy_absgrad_out is not None, batch=True)
     S, R = max(1, int(blur_samples)), max(1, int(rs_bands))
     if viewmats.dim() != 4 or tuple(viewmats.shape[1:]) != (S * R, 4, 4):
         raise ValueError(f"viewmats must be [B,{S * R},4,4] (B cameras x {S} blur samples x {R} row bands)")
@@ -1833,19 +1898,16 @@ def render_batch(means3d: Tensor, scales: Tensor, quats: Tensor, opacities: Tens
         raise ValueError(f"xy_grad_out must be [B,N,2] = [{B},{N},2]")
     if xy_absgrad_out is not None and tuple(xy_absgrad_out.shape) != (B, N, 2):
         raise ValueError(f"xy_absgrad_out must be [B,N,2] = [{B},{N},2]")
+    # B == 1 is render_combined; B > 1: one frame of B * S sample images whose viewmats span all the cameras
+    spec = FrameSpec.of(B * S, R, fx, fy, cx, cy, H, W, sh_degree=sh_degree, antialiased=antialiased,
+                        glob_scale=glob_scale, clip_thresh=clip_thresh, gamma=gamma, min_rgb_level=min_rgb_level,
+                        return_alpha=return_alpha, return_depth=return_depth, raw_params=raw_params, cameras=B)
     if B == 1:
-        out = _RenderSubposes.apply(means3d, scales, quats, opacities, sh, viewmats[0], background, S, R, fx, fy, cx, cy,
-                                    H, W, sh_degree, antialiased, glob_scale, clip_thresh,
-                                    None if xy_grad_out is None else xy_grad_out[0], bool(return_alpha), float(gamma),
-                                    float(min_rgb_level), None, None, None, bool(return_depth), 0.0, sh_rest,
-                                    3 if raw_params else 0, False, hints, 1,
-                                    None if xy_absgrad_out is None else xy_absgrad_out[0])
-    else:
-        out = _RenderSubposes.apply(means3d, scales, quats, opacities, sh, viewmats.reshape(B * S * R, 4, 4), background,
-                                    B * S, R, fx, fy, cx, cy, H, W, sh_degree, antialiased, glob_scale, clip_thresh,
-                                    xy_grad_out, bool(return_alpha), float(gamma), float(min_rgb_level), None, None, None,
-                                    bool(return_depth), 0.0, sh_rest, 3 if raw_params else 0, False, hints, B,
-                                    xy_absgrad_out)
+        xy_grad_out = None if xy_grad_out is None else xy_grad_out[0]
+        xy_absgrad_out = None if xy_absgrad_out is None else xy_absgrad_out[0]
+    out = _render_frame(spec, FrameExtras(None, xy_grad_out, xy_absgrad_out, hints), means=means3d, scales=scales,
+                        quats=quats, opacities=opacities, sh=sh, sh_rest=sh_rest,
+                        viewmats=viewmats.reshape(B * S * R, 4, 4), background=background)
     rgb, alphas, radii, depth = out
     rgb = rgb.reshape(B, H, W, 3)
     alphas = alphas.reshape(B, S, H, W) if alphas is not None else None

@@ -3,10 +3,10 @@
 `ops.render_combined` is an autograd node: a training iteration then crosses Python's autograd machinery between the
 forward and the backward compositor — the engine's worker-thread hand-off, the loss's own nodes, allocator calls —
 while the GPU queue is EMPTY (the forward ends with a host read-back).  On the 1M-Gaussian benchmark frame that window
-was ~0.1 ms of a 2.2 ms step.  `render_step` issues the same C-ABI calls (the very same forward / backward bodies of
-ops._RenderSubposes and ops._SubposeViewmats, driven through a plain context object) back to back: sub-pose viewmats ->
-projection -> frame forward -> sub-frame average -> [d loss / d image] -> frame backward -> projection backward ->
-sub-pose backward.  Results are bit-identical to the autograd route (tests/test_gpu_parity.py::
+was ~0.1 ms of a 2.2 ms step.  `render_step` issues the same C-ABI calls (the plain functions the autograd nodes wrap,
+ops.frame_forward / frame_backward and ops.subpose_forward / subpose_backward, called directly) back to back: sub-pose
+viewmats -> projection -> frame forward -> sub-frame average -> [d loss / d image] -> frame backward -> projection
+backward -> sub-pose backward.  Results are bit-identical to the autograd route (tests/test_gpu_parity.py::
 test_render_step_equals_autograd_route); what the loss contributes is either a fixed gradient image or a callable
 (e.g. the HIP L1 + SSIM kernel of fused.py, whose forward already produces the gradient).
 """
@@ -18,23 +18,6 @@ import torch
 from torch import Tensor
 
 from . import ops
-
-
-class _Ctx:
-    """what torch.autograd.Function hands its static methods, for running them without autograd"""
-
-    def __init__(self, needs_input_grad):
-        self.needs_input_grad = tuple(needs_input_grad)
-        self.saved_tensors = ()
-
-    def save_for_backward(self, *tensors):
-        self.saved_tensors = tensors
-
-    def mark_non_differentiable(self, *tensors):
-        pass
-
-    def set_materialize_grads(self, value):
-        pass
 
 
 @torch.no_grad()
@@ -70,27 +53,28 @@ def render_step(means: Tensor, scales: Tensor, quats: Tensor, opacities: Tensor,
     pixvel = motion_model == "pixel_velocity"
     if not pixvel and motion_model != "se3":
         raise ValueError(f"unknown motion_model {motion_model!r}")
-    if pixvel and xy_absgrad_out is not None:
-        raise ValueError("xy_absgrad_out is not available with the pixel-velocity model: its backward compositor uses "
-                         "gradient slots 9 and 10 for d loss / d pixel velocity")
     if times_grad and (pixvel or shared_list or float(rolling_shutter_time) != 0.0):
         raise ValueError("times_grad is available with the SE(3) motion model only: the pixel-velocity model, the shared "
                          "list and exact rolling shutter take the sub-pose times inside their projection / compositors")
-    sub_ctx = None
+    depth = grad_depth is not None                      # the alphas are returned for the depth loss only
+    spec = ops.FrameSpec.of(S, R, fx, fy, cx, cy, img_height, img_width, sh_degree=sh_degree, antialiased=antialiased,
+                            glob_scale=glob_scale, clip_thresh=clip_thresh, gamma=gamma, min_rgb_level=min_rgb_level,
+                            return_alpha=depth, return_depth=depth, rs_time=rolling_shutter_time, raw_params=raw_params,
+                            shared_list=shared_list)
+    ops._validate_frame(pixvel=pixvel, R=R, rs_time=spec.rs_time, shared_list=spec.shared_list,
+                        absgrad=xy_absgrad_out is not None, batch=False)
+    sub_saved = None
     if pixvel:
         vms = viewmat
     else:
-        sub_ctx = _Ctx((camera_grads, camera_grads, camera_grads, bool(times_grad)))
-        vms = ops._SubposeViewmats.forward(sub_ctx, viewmat, lin_vel, ang_vel, times)
-    needs = [True, True, True, True, True, camera_grads or bool(times_grad), background is not None and background_grad] + [False] * 16 + \
-            [camera_grads and pixvel, camera_grads and pixvel, False, False, False, sh_rest is not None, False, False]
-    ctx = _Ctx(needs)
-    depth = grad_depth is not None
-    rgb, alphas, radii, depth_acc = ops._RenderSubposes.forward(
-        ctx, means, scales, quats, opacities, sh, vms, background, S, R, fx, fy, cx, cy, img_height, img_width,
-        sh_degree, antialiased, glob_scale, clip_thresh, xy_grad_out, depth, float(gamma), float(min_rgb_level),
-        lin_vel if pixvel else None, ang_vel if pixvel else None, times if pixvel else None, depth,
-        float(rolling_shutter_time), sh_rest, 3 if raw_params else 0, bool(shared_list), hints, 1, xy_absgrad_out)
+        vms, sub_saved = ops.subpose_forward(viewmat, lin_vel, ang_vel, times)
+    want = {"gaussians": True, "viewmats": camera_grads or times_grad, "twist": camera_grads and pixvel,
+            "background": background is not None and background_grad, "sh_rest": sh_rest is not None}
+    (rgb, alphas, radii, depth_acc), state, saved = ops.frame_forward(
+        spec, means, scales, quats, opacities, sh, sh_rest=sh_rest, viewmats=vms, background=background,
+        lin_vel=lin_vel if pixvel else None, ang_vel=ang_vel if pixvel else None,
+        want=frozenset(k for k, v in want.items() if v), times=times if pixvel else None, xy_grad_out=xy_grad_out,
+        xy_absgrad_out=xy_absgrad_out, hints=hints)
     if callable(grad_image):
         # the callable may use torch.autograd itself (rgb.requires_grad_() + autograd.grad): it sees a detached leaf and
         # runs with gradient recording on (under this function's no_grad it silently got None)
@@ -114,15 +98,15 @@ def render_step(means: Tensor, scales: Tensor, quats: Tensor, opacities: Tensor,
         v_depth = grad_depth
     if v_depth is not None and tuple(v_depth.shape) != (S, img_height, img_width):
         raise ValueError(f"d loss / d depth_acc must be [S,H,W] = {(S, img_height, img_width)}, got {tuple(v_depth.shape)}")
-    g = ops._RenderSubposes.backward(ctx, v_rgb, v_alpha, None, v_depth)
-    grads = {"means": g[0], "scales": g[1], "quats": g[2], "opacities": g[3], "sh": g[4], "background": g[6],
-             "sh_rest": g[28], "viewmat": None, "lin_vel": None, "ang_vel": None}
+    g = ops.frame_backward(state, saved, v_rgb, v_alpha, v_depth)
+    grads = {"means": g.means, "scales": g.scales, "quats": g.quats, "opacities": g.opacities, "sh": g.sh,
+             "background": g.background, "sh_rest": g.sh_rest, "viewmat": None, "lin_vel": None, "ang_vel": None}
     if times_grad:
         grads["times"] = None
     if pixvel:
-        grads["viewmat"], grads["lin_vel"], grads["ang_vel"] = g[5], g[23], g[24]
-    elif (camera_grads or times_grad) and g[5] is not None:
-        v_V, v_lin, v_ang, v_times = ops._SubposeViewmats.backward(sub_ctx, g[5])
+        grads["viewmat"], grads["lin_vel"], grads["ang_vel"] = g.viewmats, g.lin_vel, g.ang_vel
+    elif (camera_grads or times_grad) and g.viewmats is not None:
+        v_V, v_lin, v_ang, v_times = ops.subpose_backward(sub_saved, g.viewmats, bool(times_grad))
         if camera_grads:
             grads["viewmat"], grads["lin_vel"], grads["ang_vel"] = v_V, v_lin, v_ang
         if times_grad:

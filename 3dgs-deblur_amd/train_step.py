@@ -390,15 +390,7 @@ def train_step(model: SplatfactoDeblurModel, optimizers: Dict[str, torch.optim.O
             loss = loss + tv
         loss.backward()
     if allreduce is not None:
-        from . import dp
-        dp.allreduce_gradients(list(model.gauss_params().values()), mode=allreduce, average=True)
-        # the parameters that are not per-Gaussian rows (learnable background, pose / velocity adjustments) see
-        # only this rank's views too: one small dense bucket, or the replicas drift apart silently
-        small = _small_params(model)
-        for p in small:
-            if p.grad is None:
-                p.grad = torch.zeros_like(p)
-        dp.allreduce_dense_([p.grad for p in small], average=True)
+        _dp_allreduce(model, allreduce)
     optimizers_step(optimizers.values(), row_mask=selection_mask(model, optimizers.values(), allreduce))
     model.step += 1
     # ONE read-back for the step's two log values (each .item() is a stream synchronisation)
@@ -410,6 +402,8 @@ def train_step(model: SplatfactoDeblurModel, optimizers: Dict[str, torch.optim.O
 def _dp_allreduce(model: SplatfactoDeblurModel, allreduce: str) -> None:
     from . import dp
     dp.allreduce_gradients(list(model.gauss_params().values()), mode=allreduce, average=True)
+    # the parameters that are not per-Gaussian rows (learnable background, pose / velocity adjustments) see
+    # only this rank's views too: one small dense bucket, or the replicas drift apart silently
     small = _small_params(model)
     for p in small:
         if p.grad is None:

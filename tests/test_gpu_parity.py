@@ -2755,7 +2755,6 @@ def _full_size_vs_oracle_fixture(gs, oracle, dev, name):
                 rows_l[cv].append(rws)
                 vals_l[cv].append(arr.astype(np.float64))
     v_img = v_img.float().to(dev)
-    from gsdeblur_amd import step as step_mod
     comp = (("centre", slice(0, 2)), ("conic", slice(2, 5)), ("opacity", slice(5, 6)), ("colour", slice(6, 9)))
 
     def unpack(v_records, touched):
@@ -2783,16 +2782,14 @@ def _full_size_vs_oracle_fixture(gs, oracle, dev, name):
                                              ops._ptr(v_rec), P * N, ops._bwd_variant(), ops._stream()), "rasterize_bwd")
             got_a = unpack(v_rec, None)[idx].cpu().numpy().astype(np.float64)
             # (c2) the default path: frame forward + frame backward, record gradients before the projection backward
-            needs = [True] * 5 + [False] * 27
-            ctx = step_mod._Ctx(needs)
-            ops._RenderSubposes.forward(ctx, means, scales, quats, opac, sh, vms, None, S, R, sc["fx"], sc["fy"], sc["cx"],
-                                        sc["cy"], H, W, 3, True, 1.0, 0.01, None, False, None, 0.0)
-            saved = ctx.saved_tensors
-            pre = ctx.prealloc
-            ops.native_frame_backward(ctx.frame, saved[6], saved[10], saved[9], saved[11], v_img, None, pre["v_records"],
+            spec = ops.FrameSpec.of(S, R, sc["fx"], sc["fy"], sc["cx"], sc["cy"], H, W, return_alpha=False)
+            _, st, t = ops.frame_forward(spec, means, scales, quats, opac, sh, viewmats=vms,
+                                         want=frozenset(["gaussians"]))
+            pre = st.prealloc
+            ops.native_frame_backward(st.frame, t.records, t.bg, t.edges, t.out_T, v_img, None, pre["v_records"],
                                       pre["touched"], None)
             got_b = unpack(pre["v_records"], pre["touched"])[idx].cpu().numpy().astype(np.float64)
-            n_slices_b = int(ctx.frame["state"].n_slices)
+            n_slices_b = int(st.frame["state"].n_slices)
         msg = {}
         for tag, got in (("unculled lists", got_a), ("default path", got_b)):
             for cname, sl in comp:
@@ -2853,6 +2850,49 @@ def test_render_step_equals_autograd_route(gs, oracle, dev, model):
         assert torch.equal(g[name], p[k].grad), k
     for k in ("viewmat", "lin_vel", "ang_vel"):
         assert rel_max(g[k].cpu(), p[k].grad.cpu()) < 1e-5, k
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", ["se3", "pixel_velocity", "pixel_velocity_rs", "shared_list"])
+def test_render_step_equals_autograd_route_with_sh_rest_and_background(gs, oracle, dev, case):
+    """the inputs test_render_step_equals_autograd_route does not reach — sh_rest beside features_dc, a learnable
+    background, the twist of the pixel-velocity forms (exact rolling shutter, shared list) — at the smallest frame with
+    more than one tile and sub-pose (3 x 2 tiles, S = 2): same image, bit-equal Gaussian-row, sh_rest and background
+    gradients on both routes, camera-level gradients to the bar of that test"""
+    O = oracle
+    n, W, H, S = 300, 48, 32, 2
+    sc = O.synthetic_scene(n, W, H, seed=92, scale_mult=6.0)
+    sc["lin_vel"], sc["ang_vel"] = sc["lin_vel"] * 20, sc["ang_vel"] * 10
+    sc["sh_dc"], sc["sh_rest"], sc["background"] = sc["sh"][:, 0], sc["sh"][:, 1:], torch.tensor([0.2, 0.5, 0.3])
+    times, _, _ = gs.subpose_schedule(S, 1 / 60, 1, 0.0)
+    tt = torch.tensor(times, device=dev)
+    wt = torch.rand(H, W, 3, generator=torch.Generator().manual_seed(5)).to(dev)
+    pixvel = case != "se3"
+    mode = dict(rolling_shutter_time=0.01 if case == "pixel_velocity_rs" else 0.0, shared_list=case == "shared_list")
+    names = ["means", "log_scales", "quats", "opacity_logits", "sh_dc", "sh_rest", "background", "viewmat", "lin_vel",
+             "ang_vel"]
+    p = {k: sc[k].float().to(dev).contiguous().clone().requires_grad_(True) for k in names}
+    if pixvel:
+        vms, cam = p["viewmat"], dict(lin_vel=p["lin_vel"], ang_vel=p["ang_vel"], times=tt)
+    else:
+        vms, cam = gs.subpose_viewmats(p["viewmat"], p["lin_vel"], p["ang_vel"], tt), {}
+    rgb, _, _ = gs.render_combined(p["means"], p["log_scales"], p["quats"], p["opacity_logits"], p["sh_dc"], vms,
+                                   p["background"], S, 1, sc["fx"], sc["fy"], sc["cx"], sc["cy"], H, W, gamma=2.2,
+                                   min_rgb_level=10.0, return_alpha=False, raw_params=True, sh_rest=p["sh_rest"], **cam,
+                                   **mode)
+    rgb.backward(wt)
+    q = {k: v.detach().clone() for k, v in p.items()}
+    rgb2, g, _ = gs.render_step(q["means"], q["log_scales"], q["quats"], q["opacity_logits"], q["sh_dc"], q["viewmat"],
+                                q["lin_vel"], q["ang_vel"], tt, q["background"], S, 1, sc["fx"], sc["fy"], sc["cx"],
+                                sc["cy"], H, W, wt, gamma=2.2, min_rgb_level=10.0, sh_rest=q["sh_rest"],
+                                motion_model="pixel_velocity" if pixvel else "se3", background_grad=True, **mode)
+    assert torch.equal(rgb2, rgb.detach()) and int((rgb2 != p["background"].detach()).any(-1).sum()) > 100
+    for k, name in (("means", "means"), ("log_scales", "scales"), ("quats", "quats"), ("opacity_logits", "opacities"),
+                    ("sh_dc", "sh"), ("sh_rest", "sh_rest"), ("background", "background")):
+        assert g[name].abs().max() > 0 and torch.equal(g[name], p[k].grad), (case, k)
+    for k in ("viewmat", "lin_vel", "ang_vel"):
+        print(f"[{case}] {k}: rel_max {rel_max(g[k].cpu(), p[k].grad.cpu()):.3g}")
+        assert rel_max(g[k].cpu(), p[k].grad.cpu()) < 1e-5, (case, k)
 
 
 def test_render_step_callable_may_use_autograd(gs, oracle, dev):
