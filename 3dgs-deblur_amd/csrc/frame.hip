@@ -19,38 +19,12 @@
 #include <atomic>
 #include <mutex>
 #include <vector>
-#include "../../include/gsdeblur.h"
-
-#define GS_OK 0
-#define GS_ERR_INVALID 1
-#define GS_ERR_WORKSPACE 3
-#define GS_EXPORT extern "C" __attribute__((visibility("default")))
-
-// library-internal forms of three exported entry points with a depth gradient (raster_bwd.hip, raster_rs.hip)
-extern "C" int gs_rasterize_bwd_slice_depth(const float* records, const int* sorted_vals, const int* tile_bins,
-                                            const int* band_edges, const float* background, int S, int R, int H, int W,
-                                            const float* out_T, const int* final_idx, const float* v_img,
-                                            const float* v_alpha, float* bwd_T, float* bwd_B, float* v_records,
-                                            const int* gi_of_e, float* tuples, unsigned char* flags,
-                                            const int* sorted_ids, int n_records, const unsigned char* tile_hot,
-                                            int variant, const float* cmb_scale, float cmb_gamma, float cmb_min_level,
-                                            const float* v_depth, int cameras, void* stream);
-extern "C" int gs_rasterize_bwd_rs_slice_depth(const float* records, const int* sorted_vals, const int* tile_bins,
-                                               const int* band_edges, const float* background, int S, int H, int W,
-                                               const float* out_T, const int* final_idx, const float* v_img,
-                                               const float* v_alpha, float* bwd_T, float* bwd_B, float* tuples,
-                                               unsigned char* flags, const int* sorted_ids, int n_records, int variant,
-                                               const float* cmb_scale, float cmb_gamma, float cmb_min_level,
-                                               const float* pix_vel, int N, float rolling_shutter_time,
-                                               const float* shared_list_times, const float* v_depth, void* stream);
-extern "C" int gs_reduce_grad_tuples_depth(int n_slice, const unsigned* slice_gi, const unsigned* counts,
-                                           const unsigned* cum_excl, const float* tuples, const unsigned char* flags,
-                                           float* v_records, unsigned char* touched, long long n_isect,
-                                           const float* records, int tuples_per_entry, int depth, void* stream);
+#include "gs_internal.h"     // status codes, GS_EXPORT, the library-internal *_depth prototypes; the public header
+#include "gs_math.h"         // gs::K::kTile
 
 namespace {
 
-constexpr int kTile = 16;
+constexpr int kTile = gs::K::kTile;
 constexpr int kKMax = GS_FRAME_MAX_SLICES;     // planned slices per frame (budget doubles per slice)
 constexpr int kIdsPad = 8;                     // the scalar-cache compositors read their lists in aligned groups of four
 
@@ -344,7 +318,9 @@ GS_EXPORT int gs_frame_forward(const gs_frame_desc* dp, float* records, unsigned
   const long long flag_off = ((1 + kKMax) * P * T + 3) & ~3ll;
   char* zero_blk = A.take<char>(sel_b + flag_off + 4 * kKMax);
   unsigned char* zeros_u8 = reinterpret_cast<unsigned char*>(zero_blk) + sel_b;
-  unsigned* sel_grand = reinterpret_cast<unsigned*>(zero_blk + sel_b - 256);      // frame total of bounding-box pairs
+  // frame total of bounding-box pairs (both launches that take it, gs_depth_select and gs_slice_plan_select, run only
+  // under `select`)
+  unsigned* sel_grand = select ? reinterpret_cast<unsigned*>(zero_blk + sel_b - 256) : nullptr;
   unsigned* thr_dev = select ? A.take<unsigned>(P) : nullptr;
   int* plan_dev = A.take<int>(plan_ints);
   unsigned char* tile_done_rs = R > 1 ? A.take<unsigned char>(P * T) : nullptr;
@@ -802,7 +778,7 @@ GS_EXPORT int gs_frame_backward_depth(const gs_frame_state* state, const float* 
                                         reinterpret_cast<const int*>(base + sl.bins), band_edges, background, S, H, W, out_T,
                                         reinterpret_cast<const int*>(base + sl.fidx), v_img, v_alpha, bwd_T, bwd_B, tuples,
                                         flags, reinterpret_cast<const int*>(base + sl.sorted_ids),
-                                        (int)std::min(n_rec, 2147483647ll), bwd_variant & 256, cmb_scale, cmb_gamma,
+                                        (int)std::min(n_rec, 2147483647ll), bwd_variant & GS_VARIANT_CLAMP_GRAD, cmb_scale, cmb_gamma,
                                         cmb_min_level, pix_vel, state->N, state->rolling_shutter_time,
                                         shared ? sample_times : nullptr, v_depth, st));
       } else

@@ -3,22 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "gs_math.h"
-
-#define GS_OK 0
-#define GS_ERR_INVALID 1
-#define GS_ERR_WORKSPACE 3
-// launch errors are returned as 1000 + hipError_t
-
-// bwd_variant bit of gs_frame_backward / gs_rasterize_bwd_slice: the absgrad specialisations of the backward compositor
-// (include/gsdeblur.h)
-#define GS_BWD_ABSGRAD 2048
-
-#define GS_EXPORT extern "C" __attribute__((visibility("default")))
-
-static inline int gs_launch_status() {
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? GS_OK : 1000 + (int)e;
-}
+#include "gs_internal.h"     // status codes, GS_EXPORT, gs_launch_status, variant bits, library-internal prototypes
 
 namespace gs {
 

@@ -8,8 +8,7 @@
 // Restates (absent fork sources): gsplat project_gaussians
 // forward/backward kernels, compute_sh_forward/backward (SURVEY.md §2.3, §8 a1,
 // a3, a9; App. A) and the model-level sub-pose loop (§8 a2, a10; north_star).
-#include "gs_common.h"
-#include "../../include/gsdeblur.h"     // gs_project_inputs (the prototypes are checked against these definitions)
+#include "gs_common.h"     // with it the public header: gs_project_inputs (the prototypes are checked against these definitions)
 
 namespace gs {
 
@@ -1314,6 +1313,18 @@ static inline FusedParams make_fused(int N, int P, const float* means, const flo
   return fp;
 }
 
+// The one launch of the fused forward projection (gs_project_fused_fwd, gs_project_pixvel_fwd, gs_project_records):
+// MAXB = SH bases held in registers (16 up to degree 3, 25 for degree 4); with the colour deferred the SH degree plays no
+// part and there is one instantiation.
+static int launch_fused_fwd(const FusedParams& fp, float* records, unsigned* depth_keys, int* num_tiles_hit, int* radii,
+                            void* stream) {
+  hipLaunchKernelGGL((fp.defer_color ? project_fused_fwd_kernel<16, true>
+                      : fp.deg <= 3  ? project_fused_fwd_kernel<16, false> : project_fused_fwd_kernel<25, false>),
+                     dim3((fp.N + 255) / 256), dim3(256), 0, (hipStream_t)stream, fp, records, depth_keys, num_tiles_hit,
+                     radii);
+  return gs_launch_status();
+}
+
 // Fused projection of N Gaussians under P sub-pose viewmats (+SH colour, antialiased opacity).
 //   records    [P*N*12] f32, depth_keys [P*N] u32, num_tiles_hit [P*N] i32, radii [P*N] i32 (nullable)
 GS_EXPORT int gs_project_fused_fwd(int N, int P, const float* means, const float* scales, float glob_scale,
@@ -1327,17 +1338,7 @@ GS_EXPORT int gs_project_fused_fwd(int N, int P, const float* means, const float
   FusedParams fp = make_fused(N, P, means, scales, glob_scale, quats, opacities, sh, K_stride, sh_degree, viewmats,
                               fx, fy, cx, cy, H, W, clip, antialiased, defer_color);
   fp.act = param_flags; fp.sh_rest = sh_rest;
-  dim3 grid((N + 255) / 256), block(256);
-  if (fp.defer_color)       // the SH degree plays no part: one instantiation
-    hipLaunchKernelGGL((project_fused_fwd_kernel<16, true>), grid, block, 0, (hipStream_t)stream, fp, records,
-                       depth_keys, num_tiles_hit, radii);
-  else if (sh_degree <= 3)
-    hipLaunchKernelGGL((project_fused_fwd_kernel<16, false>), grid, block, 0, (hipStream_t)stream, fp, records,
-                       depth_keys, num_tiles_hit, radii);
-  else
-    hipLaunchKernelGGL((project_fused_fwd_kernel<25, false>), grid, block, 0, (hipStream_t)stream, fp, records,
-                       depth_keys, num_tiles_hit, radii);
-  return gs_launch_status();
+  return launch_fused_fwd(fp, records, depth_keys, num_tiles_hit, radii, stream);
 }
 
 // Records of the pairs of one depth slice, for a frame projected with defer_color bit 4 (no records): see
@@ -1372,9 +1373,7 @@ GS_EXPORT int gs_project_records(int P, int N, const gs_project_inputs* in, int 
                               (in->defer_color | 1 | 2) & ~16);
   fp.act = in->param_flags;
   fp.records_only = 1;
-  hipLaunchKernelGGL((project_fused_fwd_kernel<16, true>), dim3((N + 255) / 256), dim3(256), 0, (hipStream_t)stream, fp,
-                     records, (unsigned*)nullptr, (int*)nullptr, (int*)nullptr);
-  return gs_launch_status();
+  return launch_fused_fwd(fp, records, nullptr, nullptr, nullptr, stream);     // colour deferred: <16, true>
 }
 
 // Colours (rgb = max(SH + 0.5, 0)) of the slice Gaussians with counts[j] > 0, written into their records;
@@ -1384,15 +1383,11 @@ GS_EXPORT int gs_slice_colors(int n_slice, const unsigned* slice_gi, const unsig
                               const float* viewmats, float* records, void* stream) {
   if (n_slice <= 0 || N <= 0 || sh_degree < 0 || sh_degree > 4 || (sh_degree + 1) * (sh_degree + 1) > K_stride)
     return GS_ERR_INVALID;
-  if (sh_degree <= 3) {
-    const int th = 64 * slice_colors_waves<16>();
-    hipLaunchKernelGGL(slice_colors_kernel<16>, dim3((n_slice + th - 1) / th), dim3(th), 0, (hipStream_t)stream,
-                       n_slice, slice_gi, counts, N, means, sh, sh_rest, K_stride, sh_degree, viewmats, records);
-  } else {
-    const int th = 64 * slice_colors_waves<25>();
-    hipLaunchKernelGGL(slice_colors_kernel<25>, dim3((n_slice + th - 1) / th), dim3(th), 0, (hipStream_t)stream,
-                       n_slice, slice_gi, counts, N, means, sh, sh_rest, K_stride, sh_degree, viewmats, records);
-  }
+  const bool low = sh_degree <= 3;                    // 16 SH bases in registers, 25 for degree 4
+  const int th = 64 * (low ? slice_colors_waves<16>() : slice_colors_waves<25>());
+  hipLaunchKernelGGL(low ? slice_colors_kernel<16> : slice_colors_kernel<25>, dim3((n_slice + th - 1) / th), dim3(th), 0,
+                     (hipStream_t)stream, n_slice, slice_gi, counts, N, means, sh, sh_rest, K_stride, sh_degree, viewmats,
+                     records);
   return gs_launch_status();
 }
 
@@ -1427,34 +1422,18 @@ static int launch_fused_bwd(const FusedParams& fp, int sh_degree, const float* r
   }
   dim3 grid(touched ? (N + kFusedChunk - 1) / kFusedChunk : (N + 255) / 256);
   const bool depth = (fp.flags & GS_FLAG_DEPTH_GRAD) != 0;
+  // the kernel, from {touched (sparse form), depth, sh_degree <= 3 (MAXB 16, else 25), zero-fill (sparse form only)}
+  const bool low = sh_degree <= 3;
   if (touched) {
     const bool zf = (fp.flags & GS_FLAG_ZERO_FILL) != 0;
-    if (depth) {
-      if (sh_degree <= 3 && zf)
-        hipLaunchKernelGGL((project_fused_bwd_sparse_depth_kernel<16, true>), grid, block, lds, st, fp, records, v_records, out, touched);
-      else if (sh_degree <= 3)
-        hipLaunchKernelGGL((project_fused_bwd_sparse_depth_kernel<16, false>), grid, block, lds, st, fp, records, v_records, out, touched);
-      else if (zf)
-        hipLaunchKernelGGL((project_fused_bwd_sparse_depth_kernel<25, true>), grid, block, lds, st, fp, records, v_records, out, touched);
-      else
-        hipLaunchKernelGGL((project_fused_bwd_sparse_depth_kernel<25, false>), grid, block, lds, st, fp, records, v_records, out, touched);
-    } else if (sh_degree <= 3 && zf)
-      hipLaunchKernelGGL((project_fused_bwd_sparse_kernel<16, true>), grid, block, lds, st, fp, records, v_records, out, touched);
-    else if (sh_degree <= 3)
-      hipLaunchKernelGGL((project_fused_bwd_sparse_kernel<16, false>), grid, block, lds, st, fp, records, v_records, out, touched);
-    else if (zf)
-      hipLaunchKernelGGL((project_fused_bwd_sparse_kernel<25, true>), grid, block, lds, st, fp, records, v_records, out, touched);
-    else
-      hipLaunchKernelGGL((project_fused_bwd_sparse_kernel<25, false>), grid, block, lds, st, fp, records, v_records, out, touched);
+#define GS_PICK(NAME) (low ? (zf ? NAME<16, true> : NAME<16, false>) : (zf ? NAME<25, true> : NAME<25, false>))
+    const auto kernel = depth ? GS_PICK(project_fused_bwd_sparse_depth_kernel) : GS_PICK(project_fused_bwd_sparse_kernel);
+#undef GS_PICK
+    hipLaunchKernelGGL(kernel, grid, block, lds, st, fp, records, v_records, out, touched);
   } else {
-    if (depth && sh_degree <= 3)
-      hipLaunchKernelGGL(project_fused_bwd_depth_kernel<16>, grid, block, lds, st, fp, records, v_records, out);
-    else if (depth)
-      hipLaunchKernelGGL(project_fused_bwd_depth_kernel<25>, grid, block, lds, st, fp, records, v_records, out);
-    else if (sh_degree <= 3)
-      hipLaunchKernelGGL(project_fused_bwd_kernel<16>, grid, block, lds, st, fp, records, v_records, out);
-    else
-      hipLaunchKernelGGL(project_fused_bwd_kernel<25>, grid, block, lds, st, fp, records, v_records, out);
+    const auto kernel = depth ? (low ? project_fused_bwd_depth_kernel<16> : project_fused_bwd_depth_kernel<25>)
+                              : (low ? project_fused_bwd_kernel<16> : project_fused_bwd_kernel<25>);
+    hipLaunchKernelGGL(kernel, grid, block, lds, st, fp, records, v_records, out);
   }
   if (pose) {
     // the blocks' rows, added up in block order: v_viewmats[p] (SE(3): one slot per sub-pose, 16 floats apart), or
@@ -1462,16 +1441,10 @@ static int launch_fused_bwd(const FusedParams& fp, int sh_degree, const float* r
     PoseDst dst{out.v_viewmats, fp.pixvel ? out.v_twist : nullptr, fp.pixvel ? 0 : 16, (!fp.pixvel && out.dirty) ? 1 : 0};
     hipLaunchKernelGGL(pose_reduce_kernel, dim3(slots), dim3(256), 0, st, out.pose_partial, (int)grid.x, slots, dst);
   }
-  if (needles)
-    // needles (scale ratio above kNeedleRatio) get their means / scales / quaternion gradients again, in double
-  {
-    if (depth)
-      hipLaunchKernelGGL(project_needle_hp_depth_kernel, dim3((N + kNeedleChunk - 1) / kNeedleChunk), dim3(256), 0, st, fp,
-                         records, v_records, out.v_means, out.v_scales, out.v_quats, touched, kNeedleRatio, needle_clears);
-    else
-      hipLaunchKernelGGL(project_needle_hp_kernel, dim3((N + kNeedleChunk - 1) / kNeedleChunk), dim3(256), 0, st, fp,
-                         records, v_records, out.v_means, out.v_scales, out.v_quats, touched, kNeedleRatio, needle_clears);
-  }
+  if (needles)    // needles (scale ratio above kNeedleRatio) get their means / scales / quaternion gradients again, in double
+    hipLaunchKernelGGL(depth ? project_needle_hp_depth_kernel : project_needle_hp_kernel,
+                       dim3((N + kNeedleChunk - 1) / kNeedleChunk), dim3(256), 0, st, fp, records, v_records, out.v_means,
+                       out.v_scales, out.v_quats, touched, kNeedleRatio, needle_clears);
   return gs_launch_status();
 }
 
@@ -1629,17 +1602,7 @@ GS_EXPORT int gs_project_pixvel_fwd(int N, int P, const float* means, const floa
   fp.pixvel = 1; fp.twist = twist; fp.times = times;
   fp.rs_half = 0.5f * rolling_shutter_time; fp.pix_vel_out = pix_vel;
   fp.act = param_flags; fp.sh_rest = sh_rest;
-  dim3 grid((N + 255) / 256), block(256);
-  if (fp.defer_color)       // the SH degree plays no part: one instantiation
-    hipLaunchKernelGGL((project_fused_fwd_kernel<16, true>), grid, block, 0, (hipStream_t)stream, fp, records,
-                       depth_keys, num_tiles_hit, radii);
-  else if (sh_degree <= 3)
-    hipLaunchKernelGGL((project_fused_fwd_kernel<16, false>), grid, block, 0, (hipStream_t)stream, fp, records,
-                       depth_keys, num_tiles_hit, radii);
-  else
-    hipLaunchKernelGGL((project_fused_fwd_kernel<25, false>), grid, block, 0, (hipStream_t)stream, fp, records,
-                       depth_keys, num_tiles_hit, radii);
-  return gs_launch_status();
+  return launch_fused_fwd(fp, records, depth_keys, num_tiles_hit, radii, stream);
 }
 
 // v_viewmat [16] and v_twist [12: lin 3, ang 3, 6 unused] are accumulated into (caller zeroes; nullable; with either,

@@ -653,40 +653,26 @@ using namespace gs;
 static int launch_fwd(const RasterParams& prm, const SliceState& st, const int* ids, int n_records, float* out_img,
                       float* out_T, int* final_idx, int variant, hipStream_t stream, float* out_depth = nullptr,
                       const unsigned char* tile_hot = nullptr, unsigned long long* stats = nullptr) {
-  unsigned work = (unsigned)(prm.S * prm.tiles_x * prm.tiles_y);
-  unsigned blocks = (work + 3) / 4;
+  const unsigned work = (unsigned)(prm.S * prm.tiles_x * prm.tiles_y), blocks = (work + 3) / 4;
+  const dim3 grid(blocks), block(256);
+  // the scalar-cache kernel: variant 0 with a record-index list — or n_records == 0: the caller says there is not a
+  // single list entry, every tile's range is empty and `ids` is never read (background only)
+  const bool sload = !stats && variant == 0 && (ids != nullptr || n_records == 0);
+  if (sload)
+    hipLaunchKernelGGL(out_depth ? raster_fwd_sload_kernel<true> : raster_fwd_sload_kernel<false>, grid, block, 0, stream,
+                       prm, st, ids, prm.records, (unsigned)(n_records > 0 ? n_records - 1 : 0), out_img, out_T, final_idx,
+                       blocks, out_depth, tile_hot);
 #if GS_ROUND1_KERNELS
-  if (stats) {
-    if (out_depth) return GS_ERR_INVALID;
-    hipLaunchKernelGGL((raster_fwd_slice_kernel<false, true>), dim3(blocks), dim3(256), 0, stream, prm, st, out_img,
-                       out_T, final_idx, blocks, stats);
-    return GS_OK;
-  }
-#else
-  if (stats) return GS_ERR_INVALID;
-#endif
-  // n_records == 0: the caller says there is not a single list entry — every tile's range is empty and `ids` is never
-  // read (background only)
-  const bool sload = variant == 0 && (ids != nullptr || n_records == 0);
-  if (out_depth && !sload) return GS_ERR_INVALID;                   // no depth channel in the round-1 kernel
-  if (sload && out_depth)
-    hipLaunchKernelGGL(raster_fwd_sload_kernel<true>, dim3(blocks), dim3(256), 0, stream, prm, st, ids, prm.records,
-                       (unsigned)(n_records > 0 ? n_records - 1 : 0), out_img, out_T, final_idx, blocks, out_depth,
-                       tile_hot);
-  else if (sload)
-    hipLaunchKernelGGL(raster_fwd_sload_kernel<false>, dim3(blocks), dim3(256), 0, stream, prm, st, ids, prm.records,
-                       (unsigned)(n_records > 0 ? n_records - 1 : 0), out_img, out_T, final_idx, blocks,
-                       (float*)nullptr, tile_hot);
-#if GS_ROUND1_KERNELS
-  else if (variant == 1)
-    hipLaunchKernelGGL(raster_fwd_slice_kernel<false>, dim3(blocks), dim3(256), 0, stream, prm, st, out_img, out_T,
-                       final_idx, blocks);
-  else
-    hipLaunchKernelGGL(raster_fwd_slice_kernel<true>, dim3(blocks), dim3(256), 0, stream, prm, st, out_img, out_T,
-                       final_idx, blocks);
+  else if (out_depth)
+    return GS_ERR_INVALID;                                          // no depth channel in the round-1 kernel
+  else      // stats: the counting form (gs_rasterize_fwd_slice_stats); without, `stats` is the kernels' default, NULL
+    hipLaunchKernelGGL((stats ? raster_fwd_slice_kernel<false, true>
+                        : variant == GS_VARIANT_ROUND1_PLAIN ? raster_fwd_slice_kernel<false> : raster_fwd_slice_kernel<true>),
+                       grid, block, 0, stream, prm, st, out_img, out_T, final_idx, blocks, stats);
 #else
   else
-    return GS_ERR_INVALID;      // the round-1 compositors (variant 1 / 2, or no record-index list) are not in this build
+    return GS_ERR_INVALID;      // the round-1 compositors (variant 1 / 2, the stats form, or no record-index list) are
+                                // not in this build
 #endif
   return GS_OK;
 }

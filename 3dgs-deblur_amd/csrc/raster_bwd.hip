@@ -947,36 +947,37 @@ GS_EXPORT int gs_rasterize_bwd(const float* records, const int* sorted_vals, con
                                float* v_records, int n_records, int variant, void* stream) {
   if (S <= 0 || R <= 0 || H <= 0 || W <= 0) return GS_ERR_INVALID;
   RasterParams prm = make_raster_params(records, sorted_vals, tile_bins, band_edges, background, S, R, H, W);
-  if (variant & 256) { prm.alpha_grad_max = 3.0e38f; variant &= ~256; }
-  unsigned work = (unsigned)(S * prm.tiles_x * prm.tiles_y);
-  unsigned blocks = (work + 3) / 4;
-  if (n_records == 0 && variant == 0) return GS_OK;         // not a single list entry: no gradient (v_records stays zero)
-  if (n_records > 0 && variant == 0)
-    hipLaunchKernelGGL((raster_bwd_sload_kernel<false, 0>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, prm,
-                       sorted_vals, sorted_vals, records, (unsigned)(n_records - 1), out_T, final_idx, v_img, v_alpha,
-                       v_records, blocks, (float*)nullptr, (float*)nullptr, (float*)nullptr, (unsigned char*)nullptr,
-                       (const unsigned char*)nullptr);
-  else
+  if (variant & GS_VARIANT_CLAMP_GRAD) { prm.alpha_grad_max = 3.0e38f; variant &= ~GS_VARIANT_CLAMP_GRAD; }
+  const unsigned work = (unsigned)(S * prm.tiles_x * prm.tiles_y), blocks = (work + 3) / 4;
+  const dim3 grid(blocks), block(256);
+  float* const no_f = nullptr;
+  unsigned char* const no_u8 = nullptr;
+  if (variant == 0) {
+    if (n_records == 0) return GS_OK;       // not a single list entry: no gradient (v_records stays zero)
+    if (n_records > 0) {
+      hipLaunchKernelGGL((raster_bwd_sload_kernel<false, 0>), grid, block, 0, (hipStream_t)stream, prm, sorted_vals,
+                         sorted_vals, records, (unsigned)(n_records - 1), out_T, final_idx, v_img, v_alpha, v_records,
+                         blocks, no_f, no_f, no_f, no_u8, (const unsigned char*)nullptr);
+      return gs_launch_status();
+    }
+  }
 #if GS_ROUND1_KERNELS
-    hipLaunchKernelGGL((raster_bwd_kernel_v2<false, 0>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, prm, out_T,
-                       final_idx, v_img, v_alpha, v_records, blocks, (float*)nullptr, (float*)nullptr, (float*)nullptr,
-                       (unsigned char*)nullptr);
-#else
-    return GS_ERR_INVALID;      // the round-1 backward is not in this build
-#endif
+  hipLaunchKernelGGL((raster_bwd_kernel_v2<false, 0>), grid, block, 0, (hipStream_t)stream, prm, out_T, final_idx, v_img,
+                     v_alpha, v_records, blocks, no_f, no_f, no_f, no_u8);
   return gs_launch_status();
+#else
+  return GS_ERR_INVALID;      // the round-1 backward is not in this build
+#endif
 }
 
 // One backward launch per slice, slices back to front.  bwd_T (initialised by the caller to out_T) and
 // bwd_B [S,H,W] (behind-colour . v_out, initialised to 0) carry the reverse-traversal state between launches.
-// gs_rasterize_bwd_slice_depth (library-internal: csrc/frame.hip) takes v_depth [S,H,W] = d loss / d depth_acc as well:
-// non-NULL selects the depth specialisations of the scalar-cache kernels, tuple form only (tuple slot 11 = d loss /
-// d depth); the round-1 and splat-parallel kernels have none (variant 1024 is not honoured with a depth gradient).
-// cameras > 1 (a frame of several cameras, S = cameras * samples per camera) with cmb_scale [cameras,H,W,3]: the
-// camera-indexed instantiations, tuple form and variant 0 only (anything else is refused).  Without cmb_scale (v_img
-// holds the per-sample gradients) the camera count changes nothing.
-// variant bit GS_BWD_ABSGRAD: the absgrad instantiations (tuple form, default variant only: with any of 1, 2 or 1024
-// the call is refused), which also write tuple slots 9 and 10 of every flagged tuple.
+// gs_rasterize_bwd_slice_depth (library-internal: gs_internal.h, called by csrc/frame.hip) also takes
+//   v_depth [S,H,W] = d loss / d depth_acc: non-NULL selects the depth specialisations (tuple slot 11 = d loss / d depth);
+//   cameras > 1 (a frame of several cameras, S = cameras * samples per camera) with cmb_scale [cameras,H,W,3]: the
+//     camera-indexed instantiations.  Without cmb_scale (v_img holds the per-sample gradients) the count changes nothing;
+//   variant bit GS_BWD_ABSGRAD: the absgrad instantiations, which also write tuple slots 9 and 10 of every flagged tuple.
+// Which combinations run which kernel, and which are refused, is the ONE rule block below.
 extern "C" int gs_rasterize_bwd_slice_depth(const float* records, const int* sorted_vals, const int* tile_bins,
                                             const int* band_edges, const float* background, int S, int R, int H, int W,
                                             const float* out_T, const int* final_idx, const float* v_img,
@@ -989,125 +990,67 @@ extern "C" int gs_rasterize_bwd_slice_depth(const float* records, const int* sor
   RasterParams prm = make_raster_params(records, sorted_vals, tile_bins, band_edges, background, S, R, H, W);
   prm.gi_of_e = gi_of_e;
   prm.cmb_scale = cmb_scale; prm.cmb_gamma = cmb_gamma; prm.cmb_min = cmb_min_level;
-  if (variant & 256) { prm.alpha_grad_max = 3.0e38f; variant &= ~256; }
-  unsigned work = (unsigned)(S * prm.tiles_x * prm.tiles_y);
-  unsigned blocks = (work + 3) / 4;
+  if (variant & GS_VARIANT_CLAMP_GRAD) { prm.alpha_grad_max = 3.0e38f; variant &= ~GS_VARIANT_CLAMP_GRAD; }
+  const unsigned work = (unsigned)(S * prm.tiles_x * prm.tiles_y), blocks = (work + 3) / 4;
+  const dim3 grid(blocks), block(256);
   hipStream_t st = (hipStream_t)stream;
-  const bool tup = tuples && flags && gi_of_e;
-  if (!tup && (!bwd_T || !bwd_B)) return GS_ERR_INVALID;
   // scalar-cache kernels: record index per sorted entry = sorted_ids, or sorted_vals itself when it holds Gaussian ids
   const int* ids = sorted_ids ? sorted_ids : (gi_of_e ? nullptr : sorted_vals);
   const unsigned max_id = (unsigned)(n_records > 0 ? n_records - 1 : 0);
-  if (variant & GS_BWD_ABSGRAD) {
-    // absgrad: its own instantiations, {rgb, rgb + depth} x {one camera's combine scale, one per camera}
-    if (variant != GS_BWD_ABSGRAD || n_records <= 0 || !ids || !tup) return GS_ERR_INVALID;
-    const bool cams = cameras > 1 && cmb_scale;
-    if (cams && S % cameras != 0) return GS_ERR_INVALID;
-    const int s_cam = cams ? S / cameras : S;
-    float* const bT = (bwd_T && bwd_B) ? bwd_T : nullptr;
-    float* const bB = bT ? bwd_B : nullptr;
-#define GS_LAUNCH_ABSGRAD(KERNEL, STATE, ...)                                                                           \
-    hipLaunchKernelGGL((KERNEL<STATE, 1>), dim3(blocks), dim3(256), 0, st, prm, ids, sorted_vals, records, max_id, out_T, \
-                       final_idx, v_img, v_alpha, v_records, blocks, bT, bB, tuples, flags, tile_hot, ##__VA_ARGS__)
-    if (cams && v_depth) {
-      if (bT) GS_LAUNCH_ABSGRAD(raster_bwd_absgrad_depth_cams_kernel, true, v_depth, s_cam);
-      else GS_LAUNCH_ABSGRAD(raster_bwd_absgrad_depth_cams_kernel, false, v_depth, s_cam);
-    } else if (cams) {
-      if (bT) GS_LAUNCH_ABSGRAD(raster_bwd_absgrad_cams_kernel, true, s_cam);
-      else GS_LAUNCH_ABSGRAD(raster_bwd_absgrad_cams_kernel, false, s_cam);
-    } else if (v_depth) {
-      if (bT) GS_LAUNCH_ABSGRAD(raster_bwd_absgrad_depth_kernel, true, v_depth);
-      else GS_LAUNCH_ABSGRAD(raster_bwd_absgrad_depth_kernel, false, v_depth);
-    } else {
-      if (bT) GS_LAUNCH_ABSGRAD(raster_bwd_absgrad_kernel, true);
-      else GS_LAUNCH_ABSGRAD(raster_bwd_absgrad_kernel, false);
+
+  const bool tup = tuples && flags && gi_of_e;        // tuple form (no atomics); otherwise v_records is accumulated into
+  const bool state = bwd_T && bwd_B;                  // reverse-traversal state of a frame of several slices
+  const bool sload = n_records > 0 && ids;            // the scalar-cache kernels can run
+  const bool absgrad = (variant & GS_BWD_ABSGRAD) != 0, depth = v_depth != nullptr, cams = cameras > 1 && cmb_scale;
+  // a null state pair reaches the STATE = false instantiations as null
+  float* const bT = state ? bwd_T : nullptr;
+  float* const bB = state ? bwd_B : nullptr;
+  // <STATE, OUT> of one kernel family: the state instantiation when the caller carries state, its twin otherwise.  The
+  // two have one type, so the compiler checks the argument list (with the family's trailing `extra`) against it.
+  auto launch = [&](auto* k_state, auto* k_plain, const int* eids, auto... extra) {
+    hipLaunchKernelGGL(state ? k_state : k_plain, grid, block, 0, st, prm, ids, eids, records, max_id, out_T, final_idx,
+                       v_img, v_alpha, v_records, blocks, bT, bB, tuples, flags, tile_hot, extra...);
+    return gs_launch_status();
+  };
+
+  // ---- the dispatch rule (GS_VARIANT_CLAMP_GRAD is stripped above) --------------------------------------------------
+  if (!tup && !state) return GS_ERR_INVALID;          // the atomic form exists with state only
+  if (absgrad || depth || cams) {
+    // the specialised families {absgrad} x {depth} x {cams}: scalar-cache kernels in tuple form only.  variant is
+    // GS_BWD_ABSGRAD or 0 and nothing else — except that the splat-parallel bit (no depth channel, no absgrad) is
+    // tolerated and IGNORED with a depth gradient and no absgrad: the depth kernel runs
+    if (depth && !absgrad) variant &= ~GS_VARIANT_SPLAT;
+    if (variant != (absgrad ? GS_BWD_ABSGRAD : 0) || !sload || !tup || (cams && S % cameras != 0)) return GS_ERR_INVALID;
+    const int s_cam = cams ? S / cameras : S;         // sample image s belongs to camera s / s_cam
+#define GS_FAMILY(NAME) NAME<true, 1>, NAME<false, 1>, sorted_vals
+    if (absgrad) {
+      if (depth && cams) return launch(GS_FAMILY(raster_bwd_absgrad_depth_cams_kernel), v_depth, s_cam);
+      if (cams) return launch(GS_FAMILY(raster_bwd_absgrad_cams_kernel), s_cam);
+      if (depth) return launch(GS_FAMILY(raster_bwd_absgrad_depth_kernel), v_depth);
+      return launch(GS_FAMILY(raster_bwd_absgrad_kernel));
     }
-#undef GS_LAUNCH_ABSGRAD
-    return gs_launch_status();
+    if (depth && cams) return launch(GS_FAMILY(raster_bwd_depth_cams_kernel), v_depth, s_cam);
+    if (cams) return launch(GS_FAMILY(raster_bwd_sload_cams_kernel), s_cam);
+    return launch(GS_FAMILY(raster_bwd_depth_kernel), v_depth);
   }
-  if (cameras > 1 && cmb_scale) {
-    // several cameras, fused combine: the camera-indexed instantiations (tuple form, the default variant only; the
-    // splat-parallel measurement form and the round-1 kernels read one camera's scale and refuse a batch)
-    if (S % cameras != 0) return GS_ERR_INVALID;
-    const int s_cam = S / cameras;
-    if ((variant & ~1024) || (!v_depth && variant != 0)) return GS_ERR_INVALID;
-    if (n_records <= 0 || !ids || !tup) return GS_ERR_INVALID;
-    const bool state = bwd_T && bwd_B;
-    if (v_depth && state)
-      hipLaunchKernelGGL((raster_bwd_depth_cams_kernel<true, 1>), dim3(blocks), dim3(256), 0, st, prm, ids, sorted_vals,
-                         records, max_id, out_T, final_idx, v_img, v_alpha, v_records, blocks, bwd_T, bwd_B, tuples,
-                         flags, tile_hot, v_depth, s_cam);
-    else if (v_depth)
-      hipLaunchKernelGGL((raster_bwd_depth_cams_kernel<false, 1>), dim3(blocks), dim3(256), 0, st, prm, ids, sorted_vals,
-                         records, max_id, out_T, final_idx, v_img, v_alpha, v_records, blocks, (float*)nullptr,
-                         (float*)nullptr, tuples, flags, tile_hot, v_depth, s_cam);
-    else if (state)
-      hipLaunchKernelGGL((raster_bwd_sload_cams_kernel<true, 1>), dim3(blocks), dim3(256), 0, st, prm, ids, sorted_vals,
-                         records, max_id, out_T, final_idx, v_img, v_alpha, v_records, blocks, bwd_T, bwd_B, tuples,
-                         flags, tile_hot, s_cam);
-    else
-      hipLaunchKernelGGL((raster_bwd_sload_cams_kernel<false, 1>), dim3(blocks), dim3(256), 0, st, prm, ids, sorted_vals,
-                         records, max_id, out_T, final_idx, v_img, v_alpha, v_records, blocks, (float*)nullptr,
-                         (float*)nullptr, tuples, flags, tile_hot, s_cam);
-    return gs_launch_status();
+  if (variant == 0 && sload) {
+    if (tup) return launch(GS_FAMILY(raster_bwd_sload_kernel));     // no state: the only slice
+#undef GS_FAMILY
+    return launch(raster_bwd_sload_kernel<true, 0>, raster_bwd_sload_kernel<true, 0>, ids);      // atomic form
   }
-  if (v_depth) {
-    // the depth kernels exist in the tuple form only (what gs_frame_backward_depth runs); variant bit 1024 (the
-    // splat-parallel measurement form, which has no depth channel) is not honoured here: the depth kernel runs
-    if (variant & ~1024) return GS_ERR_INVALID;
-    if (n_records <= 0 || !ids || !tup) return GS_ERR_INVALID;
-    if (bwd_T && bwd_B)
-      hipLaunchKernelGGL((raster_bwd_depth_kernel<true, 1>), dim3(blocks), dim3(256), 0, st, prm, ids, sorted_vals,
-                         records, max_id, out_T, final_idx, v_img, v_alpha, v_records, blocks, bwd_T, bwd_B, tuples,
-                         flags, tile_hot, v_depth);
-    else
-      hipLaunchKernelGGL((raster_bwd_depth_kernel<false, 1>), dim3(blocks), dim3(256), 0, st, prm, ids, sorted_vals,
-                         records, max_id, out_T, final_idx, v_img, v_alpha, v_records, blocks, (float*)nullptr,
-                         (float*)nullptr, tuples, flags, tile_hot, v_depth);
-    return gs_launch_status();
-  }
-  if (variant == 1024 && n_records > 0 && ids && tup) {
+  if (variant == GS_VARIANT_SPLAT && sload && tup) {
     // the splat-parallel formulation (measurement only: see raster_bwd_splat_kernel)
-    if (bwd_T && bwd_B)
-      hipLaunchKernelGGL((raster_bwd_splat_kernel<true>), dim3(blocks), dim3(256), 0, st, prm, ids, sorted_vals, records,
-                         max_id, out_T, final_idx, v_img, v_alpha, blocks, bwd_T, bwd_B, tuples, flags);
-    else
-      hipLaunchKernelGGL((raster_bwd_splat_kernel<false>), dim3(blocks), dim3(256), 0, st, prm, ids, sorted_vals, records,
-                         max_id, out_T, final_idx, v_img, v_alpha, blocks, (float*)nullptr, (float*)nullptr, tuples, flags);
-    return gs_launch_status();
-  }
-  if (variant == 0 && n_records > 0 && ids) {
-    if (tup) {
-      if (bwd_T && bwd_B)
-        hipLaunchKernelGGL((raster_bwd_sload_kernel<true, 1>), dim3(blocks), dim3(256), 0, st, prm, ids, sorted_vals,
-                           records, max_id, out_T, final_idx, v_img, v_alpha, v_records, blocks, bwd_T, bwd_B, tuples,
-                           flags, tile_hot);
-      else          // the only slice: no reverse-traversal state to load or store
-        hipLaunchKernelGGL((raster_bwd_sload_kernel<false, 1>), dim3(blocks), dim3(256), 0, st, prm, ids, sorted_vals,
-                           records, max_id, out_T, final_idx, v_img, v_alpha, v_records, blocks, (float*)nullptr,
-                           (float*)nullptr, tuples, flags, tile_hot);
-    } else {
-      hipLaunchKernelGGL((raster_bwd_sload_kernel<true, 0>), dim3(blocks), dim3(256), 0, st, prm, ids, ids, records,
-                         max_id, out_T, final_idx, v_img, v_alpha, v_records, blocks, bwd_T, bwd_B, tuples, flags,
-                         tile_hot);
-    }
+    hipLaunchKernelGGL(state ? raster_bwd_splat_kernel<true> : raster_bwd_splat_kernel<false>, grid, block, 0, st, prm,
+                       ids, sorted_vals, records, max_id, out_T, final_idx, v_img, v_alpha, blocks, bT, bB, tuples, flags);
     return gs_launch_status();
   }
 #if GS_ROUND1_KERNELS
-  if (tup) {
-    if (bwd_T && bwd_B)
-      hipLaunchKernelGGL((raster_bwd_kernel_v2<true, 1>), dim3(blocks), dim3(256), 0, st, prm, out_T, final_idx,
-                         v_img, v_alpha, v_records, blocks, bwd_T, bwd_B, tuples, flags);
-    else
-      hipLaunchKernelGGL((raster_bwd_kernel_v2<false, 1>), dim3(blocks), dim3(256), 0, st, prm, out_T, final_idx,
-                         v_img, v_alpha, v_records, blocks, (float*)nullptr, (float*)nullptr, tuples, flags);
-  } else {
-    hipLaunchKernelGGL((raster_bwd_kernel_v2<true, 0>), dim3(blocks), dim3(256), 0, st, prm, out_T, final_idx, v_img,
-                       v_alpha, v_records, blocks, bwd_T, bwd_B, tuples, flags);
-  }
+  // everything else (GS_VARIANT_ROUND1, or no record-index list): the round-1 kernel, tuple or atomic form
+  hipLaunchKernelGGL((!tup ? raster_bwd_kernel_v2<true, 0> : state ? raster_bwd_kernel_v2<true, 1> : raster_bwd_kernel_v2<false, 1>),
+                     grid, block, 0, st, prm, out_T, final_idx, v_img, v_alpha, v_records, blocks, bT, bB, tuples, flags);
   return gs_launch_status();
 #else
-  return GS_ERR_INVALID;        // the round-1 backward (variant 2, or no record-index list) is not in this build
+  return GS_ERR_INVALID;        // the round-1 backward (GS_VARIANT_ROUND1, or no record-index list) is not in this build
 #endif
 }
 
@@ -1130,7 +1073,7 @@ GS_EXPORT int gs_rasterize_bwd_slice(const float* records, const int* sorted_val
 // flags[e] == 2 marks tuples of gs_rasterize_bwd_slice's scalar-cache kernel, whose slot 5 is the plain sum of v_sigma:
 // the reduce turns it into the opacity gradient, -sum / records[gi].opacity (flags[e] == 1: slot 5 already is the
 // opacity gradient — gs_rasterize_bwd_rs_slice, the round-1 kernel).
-// gs_reduce_grad_tuples_depth (library-internal: csrc/frame.hip): depth != 0 also sums slot 11 (d loss / d depth, written
+// gs_reduce_grad_tuples_depth (library-internal: gs_internal.h): depth != 0 also sums slot 11 (d loss / d depth, written
 // by the depth specialisations of the compositors) into v_records[gi][11]; without it that slot is stored as 0.
 extern "C" int gs_reduce_grad_tuples_depth(int n_slice, const unsigned* slice_gi, const unsigned* counts,
                                            const unsigned* cum_excl, const float* tuples, const unsigned char* flags,
@@ -1140,21 +1083,12 @@ extern "C" int gs_reduce_grad_tuples_depth(int n_slice, const unsigned* slice_gi
   // the kernels index tuples and flags with 32-bit (entry * tuples_per_entry) offsets
   if (n_isect > 0 && n_isect * (long long)tuples_per_entry >= 4294967296ll) return GS_ERR_INVALID;
   const unsigned mult = (unsigned)tuples_per_entry;
-  if (n_isect > 32ll * n_slice) {  // few large Gaussians: one wave each
-    if (depth)
-      hipLaunchKernelGGL(reduce_tuples_wave_depth_kernel, dim3((n_slice + 3) / 4), dim3(256), 0, (hipStream_t)stream,
-                         n_slice, slice_gi, counts, cum_excl, tuples, flags, v_records, touched, records, mult);
-    else
-      hipLaunchKernelGGL(reduce_tuples_wave_kernel, dim3((n_slice + 3) / 4), dim3(256), 0, (hipStream_t)stream,
-                         n_slice, slice_gi, counts, cum_excl, tuples, flags, v_records, touched, records, mult);
-  } else {
-    if (depth)
-      hipLaunchKernelGGL(reduce_tuples_depth_kernel, dim3((n_slice + 255) / 256), dim3(256), 0, (hipStream_t)stream,
-                         n_slice, slice_gi, counts, cum_excl, tuples, flags, v_records, touched, records, mult);
-    else
-      hipLaunchKernelGGL(reduce_tuples_kernel, dim3((n_slice + 255) / 256), dim3(256), 0, (hipStream_t)stream,
-                         n_slice, slice_gi, counts, cum_excl, tuples, flags, v_records, touched, records, mult);
-  }
+  // few large Gaussians (n_isect > 32 * n_slice): one wave each; otherwise one thread each
+  const bool wave = n_isect > 32ll * n_slice;
+  const auto kernel = wave ? (depth ? reduce_tuples_wave_depth_kernel : reduce_tuples_wave_kernel)
+                           : (depth ? reduce_tuples_depth_kernel : reduce_tuples_kernel);
+  hipLaunchKernelGGL(kernel, dim3(wave ? (n_slice + 3) / 4 : (n_slice + 255) / 256), dim3(256), 0, (hipStream_t)stream,
+                     n_slice, slice_gi, counts, cum_excl, tuples, flags, v_records, touched, records, mult);
   return gs_launch_status();
 }
 

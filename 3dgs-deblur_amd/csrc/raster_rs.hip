@@ -551,19 +551,16 @@ GS_EXPORT int gs_rasterize_fwd_rs_slice(const float* records, const int* tile_bi
   RsParams rs; rs.pix_vel = pix_vel; rs.N = N; rs.rs_time = rolling_shutter_time; rs.times = shared_list_times;
   RsSliceState st; st.tile_done = tile_done; st.live_T = live_T; st.first = first; st.last = last; st.open_flag = open_flag;
   const unsigned work = (unsigned)(S * prm.tiles_x * prm.tiles_y), blocks = (work + 3) / 4;
-  if (out_depth)
-    hipLaunchKernelGGL(raster_fwd_rs_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, prm, rs, st,
-                       sorted_ids, records, (unsigned)(n_records - 1), out_img, out_T, final_idx, blocks, out_depth);
-  else
-    hipLaunchKernelGGL(raster_fwd_rs_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, prm, rs, st,
-                       sorted_ids, records, (unsigned)(n_records - 1), out_img, out_T, final_idx, blocks, (float*)nullptr);
+  hipLaunchKernelGGL(out_depth ? raster_fwd_rs_kernel<true> : raster_fwd_rs_kernel<false>, dim3(blocks), dim3(256), 0,
+                     (hipStream_t)stream, prm, rs, st, sorted_ids, records, (unsigned)(n_records - 1), out_img, out_T,
+                     final_idx, blocks, out_depth);
   return gs_launch_status();
 }
 
 // Backward of the same slice: tuples [I*12] (slots 0..8 as gs_rasterize_bwd_slice, 9..10 = d loss / d pixel velocity),
 // flags [I] zeroed by the caller — shared_list_times != NULL: tuples [I*S*12], flags [I*S], entry e / sample s at e*S+s; sorted_vals = emission index of every sorted entry; bwd_T / bwd_B as in
 // gs_rasterize_bwd_slice (both NULL for a one-slice frame); variant: + 256 = upstream alpha-clamp gradient.
-// gs_rasterize_bwd_rs_slice_depth (library-internal: csrc/frame.hip): v_depth [S,H,W] = d loss / d depth_acc, non-NULL
+// gs_rasterize_bwd_rs_slice_depth (library-internal: gs_internal.h): v_depth [S,H,W] = d loss / d depth_acc, non-NULL
 // selects the depth specialisation (tuple slot 11 = d loss / d depth).
 extern "C" int gs_rasterize_bwd_rs_slice_depth(const float* records, const int* sorted_vals, const int* tile_bins,
                                                const int* band_edges, const float* background, int S, int H, int W,
@@ -578,26 +575,18 @@ extern "C" int gs_rasterize_bwd_rs_slice_depth(const float* records, const int* 
   if ((bwd_T == nullptr) != (bwd_B == nullptr)) return GS_ERR_INVALID;
   RasterParams prm = make_raster_params(records, sorted_vals, tile_bins, band_edges, background, S, 1, H, W);
   prm.cmb_scale = cmb_scale; prm.cmb_gamma = cmb_gamma; prm.cmb_min = cmb_min_level;
-  if (variant & 256) prm.alpha_grad_max = 3.0e38f;
+  if (variant & GS_VARIANT_CLAMP_GRAD) prm.alpha_grad_max = 3.0e38f;
   RsParams rs; rs.pix_vel = pix_vel; rs.N = N; rs.rs_time = rolling_shutter_time; rs.times = shared_list_times;
   const unsigned work = (unsigned)(S * prm.tiles_x * prm.tiles_y), blocks = (work + 3) / 4;
-  if (v_depth && bwd_T)
-    hipLaunchKernelGGL((raster_bwd_rs_depth_kernel<true>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, prm, rs,
-                       sorted_ids, sorted_vals, records, (unsigned)(n_records - 1), out_T, final_idx, v_img, v_alpha,
-                       blocks, bwd_T, bwd_B, tuples, flags, v_depth);
-  else if (v_depth)
-    hipLaunchKernelGGL((raster_bwd_rs_depth_kernel<false>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, prm, rs,
-                       sorted_ids, sorted_vals, records, (unsigned)(n_records - 1), out_T, final_idx, v_img, v_alpha,
-                       blocks, (float*)nullptr, (float*)nullptr, tuples, flags, v_depth);
-  else if (bwd_T)
-    hipLaunchKernelGGL(raster_bwd_rs_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, prm, rs,
-                       sorted_ids, sorted_vals, records, (unsigned)(n_records - 1), out_T, final_idx, v_img, v_alpha,
-                       blocks, bwd_T, bwd_B, tuples, flags);
-  else
-    hipLaunchKernelGGL(raster_bwd_rs_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, prm, rs,
-                       sorted_ids, sorted_vals, records, (unsigned)(n_records - 1), out_T, final_idx, v_img, v_alpha,
-                       blocks, (float*)nullptr, (float*)nullptr, tuples, flags);
-  return gs_launch_status();
+  // <STATE> of one of the two families; bwd_T and bwd_B are both given or both NULL (checked above)
+  auto launch = [&](auto* k_state, auto* k_plain, auto... extra) {
+    hipLaunchKernelGGL(bwd_T ? k_state : k_plain, dim3(blocks), dim3(256), 0, (hipStream_t)stream, prm, rs, sorted_ids,
+                       sorted_vals, records, (unsigned)(n_records - 1), out_T, final_idx, v_img, v_alpha, blocks, bwd_T,
+                       bwd_B, tuples, flags, extra...);
+    return gs_launch_status();
+  };
+  if (v_depth) return launch(raster_bwd_rs_depth_kernel<true>, raster_bwd_rs_depth_kernel<false>, v_depth);
+  return launch(raster_bwd_rs_kernel<true>, raster_bwd_rs_kernel<false>);
 }
 
 GS_EXPORT int gs_rasterize_bwd_rs_slice(const float* records, const int* sorted_vals, const int* tile_bins,

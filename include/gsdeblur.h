@@ -46,7 +46,8 @@ extern "C" {
 
 /* bwd_variant bit of gs_rasterize_bwd_slice / gs_frame_backward / gs_frame_backward_depth: run the absgrad
  * specialisations of the backward compositor (tuple form, otherwise-default variant: + 256 is allowed, the round-1 and
- * splat-parallel forms are refused; SE(3) frames only).  A variant bit and not a sibling entry point: the request changes
+ * splat-parallel forms are refused; SE(3) frames only — the one rule that decides what runs and what is refused is the
+ * dispatch block of gs_rasterize_bwd_slice_depth, csrc/raster_bwd.hip).  A variant bit and not a sibling entry point: the request changes
  * which compositor instantiation runs and nothing else — no new argument travels with it — which is what the variant
  * word already selects, so every existing prototype stays as it is. */
 #define GS_BWD_ABSGRAD 2048
@@ -697,7 +698,8 @@ int gs_frame_backward(const gs_frame_state* state, const float* records, const f
  * the sum over the blended splats of weight * camera-space depth; depth is a fourth colour channel with background 0).
  * Non-NULL: v_records[.., 11] receives d loss / d record depth (float 9) besides the colour gradients — hand it to the
  * projection backward with grad flag 64.  NULL: exactly gs_frame_backward (which calls this with NULL).  With v_depth,
- * bwd_variant bit 1024 (the splat-parallel measurement form, no depth channel) is not honoured: the depth kernel runs. */
+ * bwd_variant bit 1024 (the splat-parallel measurement form, no depth channel) is not honoured: the depth kernel runs
+ * (the dispatch rule of csrc/raster_bwd.hip). */
 int gs_frame_backward_depth(const gs_frame_state* state, const float* records, const float* background,
                             const int* band_edges, const float* out_T, const float* v_img, const float* v_alpha,
                             const float* cmb_scale, float cmb_gamma, float cmb_min_level, int bwd_variant,

@@ -1183,6 +1183,84 @@ def test_tuple_backward_equals_atomic_backward(gs, oracle, dev):
         assert rel_max(res[1][1][k].cpu(), res[0][1][k].cpu()) < 1e-4, k
 
 
+def test_backward_compositor_refuses_and_accepts_what_it_documents(gs, dev):
+    """gs_rasterize_bwd_slice / gs_rasterize_bwd, called directly: which (variant, tuples, state, n_records) combinations
+    the dispatch rule of raster_bwd.hip refuses (GS_ERR_INVALID = 1) and which it runs (0).  One 16x16 tile, S = R = 1,
+    five records of a tiny forward; every buffer is a real device tensor of the right size, so a call that is wrongly
+    accepted is an ordinary launch."""
+    from gsdeblur_amd import ops
+    L = gs._lib.load()
+    p, st = ops._ptr, ops._stream
+    H = W = 16
+    K = 5
+    g = torch.Generator().manual_seed(3)
+    xys = (torch.rand(K, 2, generator=g) * 10 + 3).to(dev)
+    depths = torch.linspace(1.0, 2.0, K).to(dev)
+    radii = torch.full((K,), 3, dtype=torch.int32, device=dev)
+    conics = torch.tensor([[0.3, 0.05, 0.25]], device=dev).repeat(K, 1).contiguous()
+    colors = torch.rand(K, 3, generator=g).to(dev)
+    opac = torch.full((K,), 0.6, device=dev)
+    rec = torch.empty(K, ops.REC, device=dev)
+    dkeys = torch.empty(K, dtype=torch.int32, device=dev)
+    ntiles = torch.empty(K, dtype=torch.int32, device=dev)
+    ops._check(L.gs_pack_records(K, p(xys), p(depths), p(radii), p(conics), p(colors), p(opac), H, W, p(rec), p(dkeys),
+                                 p(ntiles), st()), "pack_records")
+    svals, bins, n_isect, _ = ops.bin_and_sort_records(rec, dkeys, ntiles, 1, K, H, W)
+    assert n_isect == K and bins.shape[0] == 1          # one tile, every splat on its list
+    ids = torch.zeros(K + ops.IDS_PAD, dtype=torch.int32, device=dev)        # record index per sorted entry, padded
+    ids[:K] = svals[:K]
+    eids = torch.zeros(K + ops.IDS_PAD, dtype=torch.int32, device=dev)       # emission index per sorted entry, padded
+    eids[:K] = torch.arange(K, dtype=torch.int32, device=dev)
+    gi_of_e = svals[:K].clone()                                              # emission order = sorted order
+    bg = torch.tensor([0.1, 0.2, 0.3], device=dev)
+    edges = ops._band_edges(H, 1, dev)
+    out_img = torch.empty(1, H, W, 3, device=dev)
+    out_T = torch.empty(1, H, W, device=dev)
+    fidx = torch.empty(1, H, W, dtype=torch.int32, device=dev)
+    ops._check(L.gs_rasterize_fwd(p(rec), p(ids), p(bins), p(edges), p(bg), 1, 1, H, W, p(out_img), p(out_T), p(fidx),
+                                  K, 0, st()), "rasterize_fwd")
+    assert float(out_T.min()) < 0.9                     # the splats were blended: the backward has work
+    v_img = torch.rand(1, H, W, 3, generator=g).to(dev)
+    v_rec = torch.zeros(K, ops.GRAD, device=dev)
+    tuples = torch.zeros(K * ops.GRAD, device=dev)
+    flags = torch.zeros(K, dtype=torch.uint8, device=dev)
+    hot = torch.ones(1, dtype=torch.uint8, device=dev)
+    bwd_T, bwd_B = out_T.clone(), torch.zeros(1, H, W, device=dev)
+    ABS = ops.BWD_ABSGRAD
+
+    def slice_call(variant, tup=True, state=False, n_records=K, S=1):
+        t = (gi_of_e, tuples, flags) if tup else (None, None, None)
+        b = (bwd_T, bwd_B) if state else (None, None)
+        return L.gs_rasterize_bwd_slice(p(rec), p(eids if tup else ids), p(bins), p(edges), p(bg), S, 1, H, W, p(out_T),
+                                        p(fidx), p(v_img), None, p(b[0]), p(b[1]), p(v_rec), p(t[0]), p(t[1]), p(t[2]),
+                                        p(ids), n_records, p(hot), variant, None, 1.0, 0.0, st())
+
+    refused = {
+        "absgrad + 1": slice_call(ABS | 1),
+        "absgrad + 2": slice_call(ABS | 2),
+        "absgrad + 1024": slice_call(ABS | 1024),
+        "absgrad, no tuples": slice_call(ABS, tup=False, state=True),
+        "absgrad, no records": slice_call(ABS, n_records=0),
+        "no tuples, no state": slice_call(0, tup=False, state=False),
+        "round-1 variant in the product library": slice_call(2),
+        "variant 0, no records": slice_call(0, n_records=0),
+        "splat-parallel, no tuples, state": slice_call(1024, tup=False, state=True),
+        "S = 0": slice_call(0, S=0),
+    }
+    assert all(v == 1 for v in refused.values()), refused
+    accepted = {
+        "absgrad + 256, tuples": slice_call(ABS | 256),
+        "variant 0, tuples, no state": slice_call(0),
+        "variant 0, atomic form, state": slice_call(0, tup=False, state=True),
+        # returns without launching
+        "gs_rasterize_bwd, no records": L.gs_rasterize_bwd(p(rec), p(ids), p(bins), p(edges), p(bg), 1, 1, H, W, p(out_T),
+                                                           p(fidx), p(v_img), None, p(v_rec), 0, 0, st()),
+    }
+    assert all(v == 0 for v in accepted.values()), accepted
+    torch.cuda.synchronize()
+    assert int(flags.sum()) > 0 and float(v_rec.abs().sum()) > 0      # the accepted launches did run
+
+
 def test_deferred_colour_and_compact_emission_change_nothing(gs, oracle, dev):
     """Deferred SH colouring (only emitted Gaussians are coloured) and compact emission (exact hit counts) are
     pure work-avoidance: images bit-identical, gradients equal up to summation order."""
