@@ -803,105 +803,96 @@ __device__ __noinline__ void needle_clear_touched(int N, int P, unsigned char* t
   }
 }
 
-// ONE source for project_needle_hp_kernel and its depth twin project_needle_hp_depth_kernel (grad flag 64:
-// v_records[.., 11] enters the means' double-precision chain too), instantiated by this macro (default kernel: same name,
-// same instruction stream)
-#define GS_NEEDLE_HP_KERNEL(NAME, DEPTH)                                                                                \
-__global__ __launch_bounds__(256) void NAME(FusedParams fp, const float* __restrict__ records,                          \
-    const float* __restrict__ v_records, float* __restrict__ v_means, float* __restrict__ v_scales,                    \
-    float* __restrict__ v_quats, unsigned char* __restrict__ touched, float ratio_limit, int clear_touched) {         \
-  __shared__ int list[kNeedleChunk];                                                                                          \
-  __shared__ int n_list;                                                                                                      \
-  __shared__ double part[256][9];                                                                                             \
-  if (threadIdx.x == 0) n_list = 0;                                                                                           \
-  __syncthreads();                                                                                                            \
-  const int i0 = blockIdx.x * kNeedleChunk + (int)threadIdx.x * 8;                                                            \
-  if (i0 < fp.N) {                                                                                                            \
-    unsigned long long any = ~0ull;                                                                                           \
-    if (touched) {                                                                                                            \
-      any = 0ull;                                                                                                             \
-      const bool word = (fp.N % 8) == 0 && i0 + 8 <= fp.N;                                                                    \
-      for (int p = 0; p < fp.P; ++p) {                                                                                        \
-        const unsigned char* t = touched + (size_t)p * fp.N + i0;                                                             \
-        if (word) any |= *reinterpret_cast<const unsigned long long*>(t);                                                     \
-        else for (int j = 0; j < 8 && i0 + j < fp.N; ++j) any |= (unsigned long long)t[j] << (8 * j);                         \
-      }                                                                                                                       \
-    }                                                                                                                         \
-    if (any != 0ull) {                                                                                                        \
-      for (int j = 0; j < 8 && i0 + j < fp.N; ++j) {                                                                          \
-        if (((any >> (8 * j)) & 0xFFull) == 0ull) continue;                                                                   \
-        const int i = i0 + j;                                                                                                 \
-        /* (log-scales: the ratio test in the log domain needs no exp) */                                                     \
-        const float s0 = fp.scales[3 * i], s1 = fp.scales[3 * i + 1], s2 = fp.scales[3 * i + 2];                              \
-        const float smax = fmaxf(s0, fmaxf(s1, s2)), smin = fminf(s0, fminf(s1, s2));                                         \
-        const bool needle = (fp.act & GS_ACT_LOG_SCALES) ? (smax - smin > __logf(ratio_limit)) : (smax > ratio_limit * smin); \
-        if (needle) list[atomicAdd(&n_list, 1)] = i;                                                                          \
-      }                                                                                                                       \
-    }                                                                                                                         \
-  }                                                                                                                           \
-  __syncthreads();                                                                                                            \
-  const int n = n_list;                                                                                                       \
-  if (n == 0) {                                                                                                               \
-    if (clear_touched) needle_clear_touched(fp.N, fp.P, touched);                                                                     \
-    return;                                                                                                                   \
-  }                                                                                                                           \
-  const int items_per = fp.pixvel ? 1 : fp.P;                  /* <= 256 (kMaxSubposes) */                                    \
-  const int per_round = max(1, 256 / items_per);               /* needles per round */                                        \
-  for (int base = 0; base < n; base += per_round) {                                                                           \
-    const int cnt = min(per_round, n - base);                                                                                 \
-    const int a = (int)threadIdx.x / items_per, p = (int)threadIdx.x - a * items_per;                                         \
-    if (a < cnt) {                                                                                                            \
-      double o9[9];                                                                                                           \
-      if (fp.pixvel) needle_item_pixvel<DEPTH>(fp, records, v_records, touched, list[base + a], o9);                          \
-      else needle_item_se3<DEPTH>(fp, records, v_records, touched, list[base + a], p, o9);                                    \
-_Pragma("unroll")                                                                                                             \
-      for (int j = 0; j < 9; ++j) part[threadIdx.x][j] = o9[j];                                                               \
-    }                                                                                                                         \
-    __syncthreads();                                                                                                          \
-    if ((int)threadIdx.x < cnt) {                                                                                             \
-      const int i = list[base + threadIdx.x];                                                                                 \
-      double acc[9] = {0., 0., 0., 0., 0., 0., 0., 0., 0.};                                                                   \
-      for (int pp = 0; pp < items_per; ++pp)                                                                                  \
-_Pragma("unroll")                                                                                                             \
-        for (int j = 0; j < 9; ++j) acc[j] += part[threadIdx.x * items_per + pp][j];                                          \
-      float s[3];                                                                                                             \
-  load_scales(fp, i, s);                                                                                                      \
-      const float q[4] = {fp.quats[4 * i], fp.quats[4 * i + 1], fp.quats[4 * i + 2], fp.quats[4 * i + 3]};                    \
-      double vs[3], vq[4];                                                                                                    \
-      cov3d_bwd_t<double>(s, fp.glob, q, acc + 3, vs, vq, (fp.flags & GS_FLAG_RAW_QUAT_GRAD) != 0);                           \
-      if (fp.act & GS_ACT_LOG_SCALES) { vs[0] *= (double)s[0]; vs[1] *= (double)s[1]; vs[2] *= (double)s[2]; }                \
-      for (int j = 0; j < 3; ++j) { v_means[3 * i + j] = (float)acc[j]; v_scales[3 * i + j] = (float)vs[j]; }                 \
-      for (int j = 0; j < 4; ++j) v_quats[4 * i + j] = (float)vq[j];                                                          \
-    }                                                                                                                         \
-    __syncthreads();                                                                                                          \
-  }                                                                                                                           \
-  if (clear_touched) needle_clear_touched(fp.N, fp.P, touched);                                                                       \
+// The projection backward kernels below take DEPTH (grad flag 64: v_records[.., 11] = d loss / d depth, which enters
+// the means' double-precision chain too) as a template parameter of the kernel itself: a shared __device__ body changes
+// the default kernels' instruction streams, a template parameter on the kernel does not
+// (profiles/kernel_templates_refactor.md).  DEPTH changes no signature.
+template <bool DEPTH>
+__global__ __launch_bounds__(256) void project_needle_hp_kernel(FusedParams fp, const float* __restrict__ records,
+    const float* __restrict__ v_records, float* __restrict__ v_means, float* __restrict__ v_scales,
+    float* __restrict__ v_quats, unsigned char* __restrict__ touched, float ratio_limit, int clear_touched) {
+  __shared__ int list[kNeedleChunk];
+  __shared__ int n_list;
+  __shared__ double part[256][9];
+  if (threadIdx.x == 0) n_list = 0;
+  __syncthreads();
+  const int i0 = blockIdx.x * kNeedleChunk + (int)threadIdx.x * 8;
+  if (i0 < fp.N) {
+    unsigned long long any = ~0ull;
+    if (touched) {
+      any = 0ull;
+      const bool word = (fp.N % 8) == 0 && i0 + 8 <= fp.N;
+      for (int p = 0; p < fp.P; ++p) {
+        const unsigned char* t = touched + (size_t)p * fp.N + i0;
+        if (word) any |= *reinterpret_cast<const unsigned long long*>(t);
+        else for (int j = 0; j < 8 && i0 + j < fp.N; ++j) any |= (unsigned long long)t[j] << (8 * j);
+      }
+    }
+    if (any != 0ull) {
+      for (int j = 0; j < 8 && i0 + j < fp.N; ++j) {
+        if (((any >> (8 * j)) & 0xFFull) == 0ull) continue;
+        const int i = i0 + j;
+        // (log-scales: the ratio test in the log domain needs no exp)
+        const float s0 = fp.scales[3 * i], s1 = fp.scales[3 * i + 1], s2 = fp.scales[3 * i + 2];
+        const float smax = fmaxf(s0, fmaxf(s1, s2)), smin = fminf(s0, fminf(s1, s2));
+        const bool needle = (fp.act & GS_ACT_LOG_SCALES) ? (smax - smin > __logf(ratio_limit)) : (smax > ratio_limit * smin);
+        if (needle) list[atomicAdd(&n_list, 1)] = i;
+      }
+    }
+  }
+  __syncthreads();
+  const int n = n_list;
+  if (n == 0) {
+    if (clear_touched) needle_clear_touched(fp.N, fp.P, touched);
+    return;
+  }
+  const int items_per = fp.pixvel ? 1 : fp.P;                  // <= 256 (kMaxSubposes)
+  const int per_round = max(1, 256 / items_per);               // needles per round
+  for (int base = 0; base < n; base += per_round) {
+    const int cnt = min(per_round, n - base);
+    const int a = (int)threadIdx.x / items_per, p = (int)threadIdx.x - a * items_per;
+    if (a < cnt) {
+      double o9[9];
+      if (fp.pixvel) needle_item_pixvel<DEPTH>(fp, records, v_records, touched, list[base + a], o9);
+      else needle_item_se3<DEPTH>(fp, records, v_records, touched, list[base + a], p, o9);
+#pragma unroll
+      for (int j = 0; j < 9; ++j) part[threadIdx.x][j] = o9[j];
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < cnt) {
+      const int i = list[base + threadIdx.x];
+      double acc[9] = {0., 0., 0., 0., 0., 0., 0., 0., 0.};
+      for (int pp = 0; pp < items_per; ++pp)
+#pragma unroll
+        for (int j = 0; j < 9; ++j) acc[j] += part[threadIdx.x * items_per + pp][j];
+      float s[3];
+      load_scales(fp, i, s);
+      const float q[4] = {fp.quats[4 * i], fp.quats[4 * i + 1], fp.quats[4 * i + 2], fp.quats[4 * i + 3]};
+      double vs[3], vq[4];
+      cov3d_bwd_t<double>(s, fp.glob, q, acc + 3, vs, vq, (fp.flags & GS_FLAG_RAW_QUAT_GRAD) != 0);
+      if (fp.act & GS_ACT_LOG_SCALES) { vs[0] *= (double)s[0]; vs[1] *= (double)s[1]; vs[2] *= (double)s[2]; }
+      for (int j = 0; j < 3; ++j) { v_means[3 * i + j] = (float)acc[j]; v_scales[3 * i + j] = (float)vs[j]; }
+      for (int j = 0; j < 4; ++j) v_quats[4 * i + j] = (float)vq[j];
+    }
+    __syncthreads();
+  }
+  if (clear_touched) needle_clear_touched(fp.N, fp.P, touched);
 }
 
-GS_NEEDLE_HP_KERNEL(project_needle_hp_kernel, false)
-GS_NEEDLE_HP_KERNEL(project_needle_hp_depth_kernel, true)
-
-// dense launch: one thread per Gaussian (no touched flags: every Gaussian gets its gradient written).  ONE source for
-// project_fused_bwd_kernel and its depth twin project_fused_bwd_depth_kernel (grad flag 64: v_records[.., 11] = d loss /
-// d depth), instantiated by this macro: the default kernel keeps its name and instruction stream (a shared __device__
-// body changes the latter)
-#define GS_FUSED_BWD_KERNEL(NAME, DEPTH)                                                                                \
-template <int MAXB>                                                                                                     \
-__global__ __launch_bounds__(256) void NAME(FusedParams fp, const float* __restrict__ records,                          \
-    const float* __restrict__ v_records, FusedOut out) {                                                                \
-  __shared__ float lds[48];                                                                                               \
-  extern __shared__ float blk_acc[];             /* [slots][12]: this block's pose-gradient sums (reduce_vV) */           \
-  const int slots = out.pose_partial ? (fp.pixvel ? 2 : fp.P) : 0;                                                        \
-  for (int k = threadIdx.x; k < slots * 12; k += 256) blk_acc[k] = 0.f;                                                   \
-  __syncthreads();                                                                                                        \
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;                                                                    \
-  fused_bwd_body<MAXB, DEPTH>(fp, records, v_records, out, nullptr, i, i < fp.N, lds, blk_acc);                           \
-  __syncthreads();                                                                                                        \
-  for (int k = threadIdx.x; k < slots * 12; k += 256) out.pose_partial[(size_t)blockIdx.x * slots * 12 + k] = blk_acc[k]; \
+// dense launch: one thread per Gaussian (no touched flags: every Gaussian gets its gradient written)
+template <int MAXB, bool DEPTH>
+__global__ __launch_bounds__(256) void project_fused_bwd_kernel(FusedParams fp, const float* __restrict__ records,
+    const float* __restrict__ v_records, FusedOut out) {
+  __shared__ float lds[48];
+  extern __shared__ float blk_acc[];             // [slots][12]: this block's pose-gradient sums (reduce_vV)
+  const int slots = out.pose_partial ? (fp.pixvel ? 2 : fp.P) : 0;
+  for (int k = threadIdx.x; k < slots * 12; k += 256) blk_acc[k] = 0.f;
+  __syncthreads();
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  fused_bwd_body<MAXB, DEPTH>(fp, records, v_records, out, nullptr, i, i < fp.N, lds, blk_acc);
+  __syncthreads();
+  for (int k = threadIdx.x; k < slots * 12; k += 256) out.pose_partial[(size_t)blockIdx.x * slots * 12 + k] = blk_acc[k];
 }
-
-GS_FUSED_BWD_KERNEL(project_fused_bwd_kernel, false)
-GS_FUSED_BWD_KERNEL(project_fused_bwd_depth_kernel, true)
 
 // sparse launch (touched flags): under early termination ~1 % of the Gaussians carry a gradient and they are
 // scattered, so with one thread per Gaussian nearly every wave ran the whole body for one or two lanes.  A block owns
@@ -937,7 +928,6 @@ __device__ __forceinline__ void zero_span(float* __restrict__ base, size_t first
 // (256, 2): two waves per SIMD = at most 256 VGPRs.  The body sits right at that cliff (256 with the round-3 pixel-
 // velocity VJP, 258 with round 4's — one wave per SIMD, and the zero fill of the 236 MB of gradient outputs, which is
 // most of this kernel's time on a sparse frame, dropped from 3.3 to 2.3 TB/s: 72 -> 104 us, found by an on-GPU bisect)
-// ONE source for project_fused_bwd_sparse_kernel and its depth twin project_fused_bwd_sparse_depth_kernel (grad flag 64)
 // The touched flags of the block's eight rounds are all loaded before the first ballot (their latencies overlap instead
 // of adding up; the compaction order — round, wave, lane — is what it was, and with it the order of the pose sums).
 // Pooled mode (ZERO_FILL with out.dirty, gs_project_fused_bwd_pooled): the five (six) gradient arrays are +0.0
@@ -947,106 +937,102 @@ __device__ __forceinline__ void zero_span(float* __restrict__ base, size_t first
 // dirty[g] = (some sub-pose touched g), the rows its body is about to write.  A block reads and writes its own chunk of
 // every array only: no atomics, no order between blocks.  v_xy_sum is the caller's buffer and is streamed as ever.
 // out.clear_touched: see FusedOut.
-#define GS_FUSED_BWD_SPARSE_KERNEL(NAME, DEPTH)                                                                         \
-template <int MAXB, bool ZERO_FILL>                                                                                     \
-__global__ __launch_bounds__(256, 2) void NAME(FusedParams fp,                                                          \
-    const float* __restrict__ records, const float* __restrict__ v_records, FusedOut out,                               \
-    unsigned char* __restrict__ touched /* [P*N] */) {                                                                  \
-  __shared__ float lds[48];                                                                                               \
-  __shared__ int list[kFusedChunk];                                                                                       \
-  __shared__ int wave_cnt[kFusedChunk / 256][4];                                                                          \
-  __shared__ int n_dirty;                                                                                                 \
-  extern __shared__ float blk_acc[];             /* [slots][12]: this block's pose-gradient sums (reduce_vV) */           \
-  const int slots = out.pose_partial ? (fp.pixvel ? 2 : fp.P) : 0;                                                        \
-  for (int k = threadIdx.x; k < slots * 12; k += 256) blk_acc[k] = 0.f;                                                   \
-  const int lane = lane_id(), wave = threadIdx.x >> 6;                                                                    \
-  const int base = blockIdx.x * kFusedChunk;                                                                              \
-  const int g_first = base + (int)threadIdx.x;   /* this thread's Gaussian of round r: g_first + 256 r */                 \
-  unsigned any_m = 0u;                           /* bit r: some sub-pose touched it */                                    \
-  for (int p = 0; p < fp.P; ++p) {                                                                                        \
-    const unsigned char* t = touched + (size_t)p * fp.N;                                                                  \
-    unsigned char v[kFusedChunk / 256];                                                                                   \
-_Pragma("unroll")                                                                                                         \
-    for (int r = 0; r < kFusedChunk / 256; ++r) v[r] = t[min(g_first + r * 256, fp.N - 1)];                               \
-_Pragma("unroll")                                                                                                         \
-    for (int r = 0; r < kFusedChunk / 256; ++r) any_m |= (v[r] != 0 && g_first + r * 256 < fp.N) ? (1u << r) : 0u;        \
-  }                                                                                                                       \
-  if (ZERO_FILL) {                                                                                                        \
-    const size_t g0 = (size_t)base, cnt = (size_t)min(kFusedChunk, fp.N - base);                                          \
-    const size_t sh_row = out.v_sh_rest ? 3 : (size_t)fp.K_stride * 3, rest_row = (size_t)(fp.K_stride - 1) * 3;         \
-    bool stream = true;                                                                                                   \
-    if (out.dirty) {                                                                                                      \
-      if (threadIdx.x == 0) n_dirty = 0;                                                                                  \
-      __syncthreads();                                                                                                    \
-      unsigned char d[kFusedChunk / 256];                                                                                 \
-_Pragma("unroll")                                                                                                         \
-      for (int r = 0; r < kFusedChunk / 256; ++r) d[r] = out.dirty[min(g_first + r * 256, fp.N - 1)];                     \
-      unsigned dirty_m = 0u;                                                                                              \
-_Pragma("unroll")                                                                                                         \
-      for (int r = 0; r < kFusedChunk / 256; ++r) dirty_m |= (d[r] != 0 && g_first + r * 256 < fp.N) ? (1u << r) : 0u;    \
-      if (dirty_m) atomicAdd(&n_dirty, __popc(dirty_m));                                                                  \
-      __syncthreads();                                                                                                    \
-      stream = (size_t)n_dirty * 4 > cnt;                                                                                 \
-      if (!stream) {                                                                                                      \
-        for (int r = 0; r < kFusedChunk / 256; ++r) {                                                                     \
-          if (!((dirty_m >> r) & 1u)) continue;                                                                           \
-          const size_t g = (size_t)(g_first + r * 256);                                                                   \
-          zero_span(out.v_means, 3 * g, 3);                                                                               \
-          zero_span(out.v_scales, 3 * g, 3);                                                                              \
-          zero_span(out.v_quats, 4 * g, 4);                                                                               \
-          out.v_opac[g] = 0.f;                                                                                            \
-          zero_span(out.v_sh, sh_row * g, sh_row);                                                                        \
-          if (out.v_sh_rest) zero_span(out.v_sh_rest, rest_row * g, rest_row);                                            \
-        }                                                                                                                 \
-      }                                                                                                                   \
-      /* the map of what this call leaves behind: the rows of the touched Gaussians, written by the body below */         \
-      for (int r = 0; r < kFusedChunk / 256; ++r)                                                                         \
-        if (((dirty_m ^ any_m) >> r) & 1u) out.dirty[g_first + r * 256] = (unsigned char)((any_m >> r) & 1u);             \
-    }                                                                                                                     \
-    if (stream) {                                                                                                         \
-      zero_rows(out.v_means, 3 * g0, 3 * cnt);                                                                            \
-      zero_rows(out.v_scales, 3 * g0, 3 * cnt);                                                                           \
-      zero_rows(out.v_quats, 4 * g0, 4 * cnt);                                                                            \
-      zero_rows(out.v_opac, g0, cnt);                                                                                     \
-      zero_rows(out.v_sh, sh_row * g0, sh_row * cnt);                                                                     \
-      if (out.v_sh_rest) zero_rows(out.v_sh_rest, rest_row * g0, rest_row * cnt);                                         \
-    }                                                                                                                     \
-    zero_rows(out.v_xy_sum, 2 * g0, 2 * cnt);                                                                             \
-    /* the rows of this block's touched Gaussians are written again below, by other threads of the block */               \
-    __threadfence_block();                                                                                                \
-  }                                                                                                                       \
-_Pragma("unroll")                                                                                                         \
-  for (int r = 0; r < kFusedChunk / 256; ++r) {                                                                           \
-    const unsigned long long bal = __ballot((any_m >> r) & 1u);                                                           \
-    if (lane == 0) wave_cnt[r][wave] = __popcll(bal);                                                                     \
-  }                                                                                                                       \
-  __syncthreads();                                                                                                        \
-  int n_list = 0;                                                                                                         \
-_Pragma("unroll")                                                                                                         \
-  for (int r = 0; r < kFusedChunk / 256; ++r) {                                                                           \
-    const bool any = (any_m >> r) & 1u;                                                                                   \
-    const unsigned long long bal = __ballot(any);                                                                         \
-    int off = n_list, total = 0;                                                                                          \
-_Pragma("unroll")                                                                                                         \
-    for (int w = 0; w < 4; ++w) { const int c = wave_cnt[r][w]; if (w < wave) off += c; total += c; }                     \
-    if (any) list[off + __popcll(bal & ((1ull << lane) - 1ull))] = g_first + r * 256;                                     \
-    n_list += total;                                                                                                      \
-  }                                                                                                                       \
-  __syncthreads();                                                                                                        \
-  for (int k0 = 0; k0 < n_list; k0 += 256) {                                                                              \
-    const int k = k0 + (int)threadIdx.x;                                                                                  \
-    const bool live = k < n_list;                                                                                         \
-    fused_bwd_body<MAXB, DEPTH>(fp, records, v_records, out, touched, live ? list[k] : 0, live, lds, blk_acc);            \
-    /* (a thread's body reads the flags of its own Gaussian only) */                                                      \
-    if (out.clear_touched && live)                                                                                        \
-      for (int p = 0; p < fp.P; ++p) touched[(size_t)p * fp.N + list[k]] = 0;                                             \
-  }                                                                                                                       \
-  __syncthreads();                                                                                                        \
-  for (int k = threadIdx.x; k < slots * 12; k += 256) out.pose_partial[(size_t)blockIdx.x * slots * 12 + k] = blk_acc[k]; \
+template <int MAXB, bool ZERO_FILL, bool DEPTH>
+__global__ __launch_bounds__(256, 2) void project_fused_bwd_sparse_kernel(FusedParams fp,
+    const float* __restrict__ records, const float* __restrict__ v_records, FusedOut out,
+    unsigned char* __restrict__ touched /* [P*N] */) {
+  __shared__ float lds[48];
+  __shared__ int list[kFusedChunk];
+  __shared__ int wave_cnt[kFusedChunk / 256][4];
+  __shared__ int n_dirty;
+  extern __shared__ float blk_acc[];             // [slots][12]: this block's pose-gradient sums (reduce_vV)
+  const int slots = out.pose_partial ? (fp.pixvel ? 2 : fp.P) : 0;
+  for (int k = threadIdx.x; k < slots * 12; k += 256) blk_acc[k] = 0.f;
+  const int lane = lane_id(), wave = threadIdx.x >> 6;
+  const int base = blockIdx.x * kFusedChunk;
+  const int g_first = base + (int)threadIdx.x;   // this thread's Gaussian of round r: g_first + 256 r
+  unsigned any_m = 0u;                           // bit r: some sub-pose touched it
+  for (int p = 0; p < fp.P; ++p) {
+    const unsigned char* t = touched + (size_t)p * fp.N;
+    unsigned char v[kFusedChunk / 256];
+#pragma unroll
+    for (int r = 0; r < kFusedChunk / 256; ++r) v[r] = t[min(g_first + r * 256, fp.N - 1)];
+#pragma unroll
+    for (int r = 0; r < kFusedChunk / 256; ++r) any_m |= (v[r] != 0 && g_first + r * 256 < fp.N) ? (1u << r) : 0u;
+  }
+  if (ZERO_FILL) {
+    const size_t g0 = (size_t)base, cnt = (size_t)min(kFusedChunk, fp.N - base);
+    const size_t sh_row = out.v_sh_rest ? 3 : (size_t)fp.K_stride * 3, rest_row = (size_t)(fp.K_stride - 1) * 3;
+    bool stream = true;
+    if (out.dirty) {
+      if (threadIdx.x == 0) n_dirty = 0;
+      __syncthreads();
+      unsigned char d[kFusedChunk / 256];
+#pragma unroll
+      for (int r = 0; r < kFusedChunk / 256; ++r) d[r] = out.dirty[min(g_first + r * 256, fp.N - 1)];
+      unsigned dirty_m = 0u;
+#pragma unroll
+      for (int r = 0; r < kFusedChunk / 256; ++r) dirty_m |= (d[r] != 0 && g_first + r * 256 < fp.N) ? (1u << r) : 0u;
+      if (dirty_m) atomicAdd(&n_dirty, __popc(dirty_m));
+      __syncthreads();
+      stream = (size_t)n_dirty * 4 > cnt;
+      if (!stream) {
+        for (int r = 0; r < kFusedChunk / 256; ++r) {
+          if (!((dirty_m >> r) & 1u)) continue;
+          const size_t g = (size_t)(g_first + r * 256);
+          zero_span(out.v_means, 3 * g, 3);
+          zero_span(out.v_scales, 3 * g, 3);
+          zero_span(out.v_quats, 4 * g, 4);
+          out.v_opac[g] = 0.f;
+          zero_span(out.v_sh, sh_row * g, sh_row);
+          if (out.v_sh_rest) zero_span(out.v_sh_rest, rest_row * g, rest_row);
+        }
+      }
+      // the map of what this call leaves behind: the rows of the touched Gaussians, written by the body below
+      for (int r = 0; r < kFusedChunk / 256; ++r)
+        if (((dirty_m ^ any_m) >> r) & 1u) out.dirty[g_first + r * 256] = (unsigned char)((any_m >> r) & 1u);
+    }
+    if (stream) {
+      zero_rows(out.v_means, 3 * g0, 3 * cnt);
+      zero_rows(out.v_scales, 3 * g0, 3 * cnt);
+      zero_rows(out.v_quats, 4 * g0, 4 * cnt);
+      zero_rows(out.v_opac, g0, cnt);
+      zero_rows(out.v_sh, sh_row * g0, sh_row * cnt);
+      if (out.v_sh_rest) zero_rows(out.v_sh_rest, rest_row * g0, rest_row * cnt);
+    }
+    zero_rows(out.v_xy_sum, 2 * g0, 2 * cnt);
+    // the rows of this block's touched Gaussians are written again below, by other threads of the block
+    __threadfence_block();
+  }
+#pragma unroll
+  for (int r = 0; r < kFusedChunk / 256; ++r) {
+    const unsigned long long bal = __ballot((any_m >> r) & 1u);
+    if (lane == 0) wave_cnt[r][wave] = __popcll(bal);
+  }
+  __syncthreads();
+  int n_list = 0;
+#pragma unroll
+  for (int r = 0; r < kFusedChunk / 256; ++r) {
+    const bool any = (any_m >> r) & 1u;
+    const unsigned long long bal = __ballot(any);
+    int off = n_list, total = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) { const int c = wave_cnt[r][w]; if (w < wave) off += c; total += c; }
+    if (any) list[off + __popcll(bal & ((1ull << lane) - 1ull))] = g_first + r * 256;
+    n_list += total;
+  }
+  __syncthreads();
+  for (int k0 = 0; k0 < n_list; k0 += 256) {
+    const int k = k0 + (int)threadIdx.x;
+    const bool live = k < n_list;
+    fused_bwd_body<MAXB, DEPTH>(fp, records, v_records, out, touched, live ? list[k] : 0, live, lds, blk_acc);
+    // (a thread's body reads the flags of its own Gaussian only)
+    if (out.clear_touched && live)
+      for (int p = 0; p < fp.P; ++p) touched[(size_t)p * fp.N + list[k]] = 0;
+  }
+  __syncthreads();
+  for (int k = threadIdx.x; k < slots * 12; k += 256) out.pose_partial[(size_t)blockIdx.x * slots * 12 + k] = blk_acc[k];
 }
-
-GS_FUSED_BWD_SPARSE_KERNEL(project_fused_bwd_sparse_kernel, false)
-GS_FUSED_BWD_SPARSE_KERNEL(project_fused_bwd_sparse_depth_kernel, true)
 
 // Lazy records (round 5): the records of the n_slice (sub-pose, Gaussian) pairs a depth slice holds — pair j is depth
 // rank slice_rank(sd, j) of sorted_gi, the walk gs_slice_counts_exact makes right afterwards — projected by the SAME
@@ -1426,13 +1412,15 @@ static int launch_fused_bwd(const FusedParams& fp, int sh_degree, const float* r
   const bool low = sh_degree <= 3;
   if (touched) {
     const bool zf = (fp.flags & GS_FLAG_ZERO_FILL) != 0;
-#define GS_PICK(NAME) (low ? (zf ? NAME<16, true> : NAME<16, false>) : (zf ? NAME<25, true> : NAME<25, false>))
-    const auto kernel = depth ? GS_PICK(project_fused_bwd_sparse_depth_kernel) : GS_PICK(project_fused_bwd_sparse_kernel);
-#undef GS_PICK
+    const auto kernel =
+        depth ? (low ? (zf ? project_fused_bwd_sparse_kernel<16, true, true> : project_fused_bwd_sparse_kernel<16, false, true>)
+                     : (zf ? project_fused_bwd_sparse_kernel<25, true, true> : project_fused_bwd_sparse_kernel<25, false, true>))
+              : (low ? (zf ? project_fused_bwd_sparse_kernel<16, true, false> : project_fused_bwd_sparse_kernel<16, false, false>)
+                     : (zf ? project_fused_bwd_sparse_kernel<25, true, false> : project_fused_bwd_sparse_kernel<25, false, false>));
     hipLaunchKernelGGL(kernel, grid, block, lds, st, fp, records, v_records, out, touched);
   } else {
-    const auto kernel = depth ? (low ? project_fused_bwd_depth_kernel<16> : project_fused_bwd_depth_kernel<25>)
-                              : (low ? project_fused_bwd_kernel<16> : project_fused_bwd_kernel<25>);
+    const auto kernel = depth ? (low ? project_fused_bwd_kernel<16, true> : project_fused_bwd_kernel<25, true>)
+                              : (low ? project_fused_bwd_kernel<16, false> : project_fused_bwd_kernel<25, false>);
     hipLaunchKernelGGL(kernel, grid, block, lds, st, fp, records, v_records, out);
   }
   if (pose) {
@@ -1442,7 +1430,7 @@ static int launch_fused_bwd(const FusedParams& fp, int sh_degree, const float* r
     hipLaunchKernelGGL(pose_reduce_kernel, dim3(slots), dim3(256), 0, st, out.pose_partial, (int)grid.x, slots, dst);
   }
   if (needles)    // needles (scale ratio above kNeedleRatio) get their means / scales / quaternion gradients again, in double
-    hipLaunchKernelGGL(depth ? project_needle_hp_depth_kernel : project_needle_hp_kernel,
+    hipLaunchKernelGGL(depth ? project_needle_hp_kernel<true> : project_needle_hp_kernel<false>,
                        dim3((N + kNeedleChunk - 1) / kNeedleChunk), dim3(256), 0, st, fp, records, v_records, out.v_means,
                        out.v_scales, out.v_quats, touched, kNeedleRatio, needle_clears);
   return gs_launch_status();

@@ -392,145 +392,139 @@ __device__ __forceinline__ bool rs_bwd_entry(const RsRecB& rc, float pxf, int id
   return true;
 }
 
-// raster_bwd_rs_kernel<STATE> and its depth-gradient twin raster_bwd_rs_depth_kernel<STATE> (v_depth [S,H,W] = d loss /
-// d depth_acc, a twelfth reduced row = tuple slot 11) are ONE source, instantiated by this macro with DEPTH = false /
-// true: the default kernels keep their names and instruction streams (a shared __device__ body changes the latter).
-#define GS_RS_NO_DEPTH_PARAM
-#define GS_RS_DEPTH_PARAM , const float* __restrict__ v_depth
-#define GS_BWD_RS_KERNEL(NAME, DEPTH, DEPTH_PARAM, PROLOGUE)                                                              \
-template <bool STATE>                                                                                                   \
-__global__ __launch_bounds__(256) void NAME(                                                                            \
-    RasterParams prm, RsParams rs, const int* __restrict__ ids, const int* __restrict__ eids,                           \
-    const float* __restrict__ records, unsigned max_id, const float* __restrict__ out_T,                                \
-    const int* __restrict__ final_idx, const float* __restrict__ v_img, const float* __restrict__ v_alpha,             \
-    unsigned n_blocks, float* __restrict__ bwd_T, float* __restrict__ bwd_B, float* __restrict__ tuples,              \
-    unsigned char* __restrict__ flags DEPTH_PARAM) {                                                                    \
-  PROLOGUE                                                                                                              \
-  __shared__ __attribute__((aligned(16))) float lds_all[4 * rs_floats(DEPTH)];                                         \
-  const int lane = lane_id();                                                                                               \
-  float* red = lds_all + (threadIdx.x >> 6) * rs_floats(DEPTH);                                                             \
-  const int T = prm.tiles_x * prm.tiles_y;                                                                                  \
-  const unsigned work = (unsigned)__builtin_amdgcn_readfirstlane(                                                           \
-      (int)(xcd_remap(blockIdx.x, n_blocks) * 4u + (threadIdx.x >> 6)));                                                    \
-  if (work >= (unsigned)(prm.S * T)) return;                                                                                \
-  const int s = work / T, t = work % T;                                                                                     \
-  const int ty = t / prm.tiles_x, tx = t % prm.tiles_x;                                                                     \
-  const bool shared = rs.times != nullptr;                                                                                  \
-  const float t_s = shared ? rs.times[s] : 0.f;                                                                             \
-  int2 range = prm.tile_bins[shared ? (size_t)t : (size_t)s * T + t];                                                       \
-  range.x = __builtin_amdgcn_readfirstlane(range.x);                                                                        \
-  range.y = __builtin_amdgcn_readfirstlane(range.y);                                                                        \
-  if (range.y <= range.x) return;                                                                                           \
-  /* lane -> its four pixels, one per 8x8 quadrant: pixel k at (px0 + 8 (k & 1), py0 + 8 (k >> 1)) */                       \
-  const int px0 = tx * K::kTile + (lane & 7);                                                                               \
-  const int py0 = ty * K::kTile + (lane >> 3);                                                                              \
-  const float pxf = (float)px0 + 0.5f;                                                                                      \
-  const float bgr = prm.background[0], bgg = prm.background[1], bgb = prm.background[2];                                    \
-  RsQuad pp;                                                                                                                \
-  int my_end = range.x;                                                                                                     \
-_Pragma("unroll")                                                                                                           \
-  for (int k = 0; k < 4; ++k) {                                                                                             \
-    const int x = px0 + 8 * (k & 1), y = py0 + 8 * (k >> 1);                                                                \
-    float Tk = 1.f, Dv = 0.f, vr = 0.f, vg = 0.f, vb = 0.f, vd = 0.f;                                                       \
-    int fin = range.x;                                                                                                      \
-    if (x < prm.W && y < prm.H) {                                                                                           \
-      const size_t pix = ((size_t)s * prm.H + y) * prm.W + x;                                                               \
-      const float Tfin = out_T[pix];                                                                                        \
-      fin = min(max(final_idx[pix], range.x), range.y);      /* a stop index never leaves the tile's list */                \
-      if (DEPTH) vd = v_depth[pix];                                                                                         \
-      vr = v_img[pix * 3 + 0]; vg = v_img[pix * 3 + 1]; vb = v_img[pix * 3 + 2];                                            \
-      if (prm.cmb_scale) {                                                                                                  \
-        const size_t q = ((size_t)y * prm.W + x) * 3;                                                                       \
-        vr = combine_grad(vr, prm.cmb_scale[q + 0], prm.cmb_gamma, prm.cmb_min);                                            \
-        vg = combine_grad(vg, prm.cmb_scale[q + 1], prm.cmb_gamma, prm.cmb_min);                                            \
-        vb = combine_grad(vb, prm.cmb_scale[q + 2], prm.cmb_gamma, prm.cmb_min);                                            \
-      }                                                                                                                     \
-      const float va_out = v_alpha ? v_alpha[pix] : 0.f;                                                                    \
-      const float va = Tfin * (va_out - (bgr * vr + bgg * vg + bgb * vb));                                                  \
-      Tk = Tfin;                                                                                                            \
-      Dv = -va;                                                                                                             \
-      if (STATE) { Tk = bwd_T[pix]; Dv = bwd_B[pix] - va; }                                                                 \
-    }                                                                                                                       \
-    my_end = max(my_end, fin);                                                                                              \
-    pp.T[k] = Tk; pp.Dv[k] = Dv; pp.vr[k] = vr; pp.vg[k] = vg; pp.vb[k] = vb; pp.py[k] = (float)y + 0.5f; pp.fin[k] = fin;  \
-    pp.vd[k] = vd;                                                                                                          \
-  }                                                                                                                         \
-  pp.tau[0] = rs_tau((float)py0 + 0.5f, (float)prm.H, rs.rs_time, t_s);                                                     \
-  pp.tau[1] = rs_tau((float)(py0 + 8) + 0.5f, (float)prm.H, rs.rs_time, t_s);                                               \
-  const int wave_end = __builtin_amdgcn_readfirstlane(wave_max_i(my_end));                                                  \
-  const float agm = prm.alpha_grad_max;                                                                                     \
-  const unsigned s_base = shared ? 0u : (unsigned)s * (unsigned)rs.N;                                                       \
-  const unsigned max_g = (unsigned)(rs.N - 1);                                                                              \
-  /* shared list: the S samples' waves write the SAME entry's gradients — every (entry, sample) pair gets a tuple of its */ \
-  /* own, e * S + s (the S tuples of an entry are adjacent, a Gaussian's tuples stay one contiguous range) */               \
-  const unsigned tmul = shared ? (unsigned)prm.S : 1u, tofs = shared ? (unsigned)s : 0u;                                    \
-  const unsigned n = (unsigned)(wave_end - range.x);                                                                        \
-  if (n != 0u) {                                                                                                            \
-    constexpr int kRows = rs_comp(DEPTH);                                                                                   \
-    const int row = lane;                                    /* row-sum role: lanes 0..43 (0..47 with DEPTH) */             \
-    const int row_g = row / kRows, row_c = row - row_g * kRows;   /* row_c = tuple slot (DEPTH: 11 = d loss / d depth) */   \
-    const int4* __restrict__ ids4 = reinterpret_cast<const int4*>(ids);                                                     \
-    const int4* __restrict__ eids4 = reinterpret_cast<const int4*>(eids);                                                   \
-    auto rec = [&](int id) {                                                                                                \
-      const unsigned gi = min((unsigned)id, max_id);                                                                        \
-      return load_rs_b<DEPTH>(records, rs.pix_vel, gi, min(gi - s_base, max_g));                                            \
-    };                                                                                                                      \
-    int b = (wave_end - 1) & ~3;                                                                                            \
-    const int b_last = range.x & ~3;                                                                                        \
-    int4 idv = ids4[b >> 2];                                                                                                \
-    RsRecB a0 = rec(idv.w), a1 = rec(idv.z);                                                                                \
-    for (;;) {                                                                                                              \
-      /* pair A (entries b+3, b+2) is ready; put pair B (b+1, b) and the indices of the next (lower) group in flight */     \
-      asm volatile("" :: "s"(a0.x), "s"(a1.x), "s"(a0.pvx), "s"(a1.pvx) : "memory");                                        \
-      const RsRecB b0 = rec(idv.y), b1 = rec(idv.x);                                                                        \
-      const int4 ev = eids4[b >> 2];                                                                                        \
-      idv = ids4[max(b - 4, 0) >> 2];                                                                                       \
-      asm volatile("" ::: "memory");                                                                                        \
-      unsigned filled = 0;                                                                                                  \
-      if ((unsigned)(b + 3 - range.x) < n && rs_bwd_entry<DEPTH>(a0, pxf, b + 3, pp, red, 3, lane, agm)) filled |= 8u;      \
-      if ((unsigned)(b + 2 - range.x) < n && rs_bwd_entry<DEPTH>(a1, pxf, b + 2, pp, red, 2, lane, agm)) filled |= 4u;      \
-      asm volatile("" :: "s"(b0.x), "s"(b1.x), "s"(b0.pvx), "s"(b1.pvx), "s"(idv.x), "s"(ev.x) : "memory");                 \
-      a0 = rec(idv.w); a1 = rec(idv.z);                                                                                     \
-      asm volatile("" ::: "memory");                                                                                        \
-      if ((unsigned)(b + 1 - range.x) < n && rs_bwd_entry<DEPTH>(b0, pxf, b + 1, pp, red, 1, lane, agm)) filled |= 2u;      \
-      if ((unsigned)(b - range.x) < n && rs_bwd_entry<DEPTH>(b1, pxf, b, pp, red, 0, lane, agm)) filled |= 1u;              \
-      if (filled) {                                                                                                         \
-        __builtin_amdgcn_wave_barrier();                                                                                    \
-        if (row < kRsGroup * kRows && ((filled >> row_g) & 1u)) {                                                           \
-          const f4* rp = reinterpret_cast<const f4*>(red + row * kRsStride);                                                \
-          f4 s0 = rp[0], s1 = rp[1], s2 = rp[2], s3 = rp[3];                                                                \
-          s0 += rp[4]; s1 += rp[5]; s2 += rp[6]; s3 += rp[7];                                                               \
-          const f4 v = (s0 + s1) + (s2 + s3);                                                                               \
-          const float sum = (v.x + v.y) + (v.z + v.w);                                                                      \
-          const int id_e = row_g == 0 ? ev.x : (row_g == 1 ? ev.y : (row_g == 2 ? ev.z : ev.w));                            \
-          const size_t e = (size_t)(unsigned)id_e * tmul + tofs;                                                            \
-          tuples[e * kGradFloats + row_c] = sum;                                                                            \
-          if (row_c == 0) flags[e] = 2;                      /* 2: slot 5 is the plain sum of v_sigma */                    \
-        }                                                                                                                   \
-        __builtin_amdgcn_wave_barrier();                                                                                    \
-      }                                                                                                                     \
-      if (b <= b_last) break;                                                                                               \
-      b -= 4;                                                                                                               \
-    }                                                                                                                       \
-  }                                                                                                                         \
-  if (STATE) {                                                                                                              \
-_Pragma("unroll")                                                                                                           \
-    for (int k = 0; k < 4; ++k) {                                                                                           \
-      const int x = px0 + 8 * (k & 1), y = py0 + 8 * (k >> 1);                                                              \
-      if (x < prm.W && y < prm.H) {                                                                                         \
-        const size_t pix = ((size_t)s * prm.H + y) * prm.W + x;                                                             \
-        const float Tfin = out_T[pix];                                                                                      \
-        const float va_out = v_alpha ? v_alpha[pix] : 0.f;                                                                  \
-        const float va = Tfin * (va_out - (bgr * pp.vr[k] + bgg * pp.vg[k] + bgb * pp.vb[k]));                              \
-        bwd_T[pix] = pp.T[k];                                                                                               \
-        bwd_B[pix] = pp.Dv[k] + va;                                                                                         \
-      }                                                                                                                     \
-    }                                                                                                                       \
-  }                                                                                                                         \
+// raster_bwd_rs_kernel<STATE, DEPTH>: DEPTH = a depth gradient is present (v_depth [S,H,W] = d loss / d depth_acc, a
+// twelfth reduced row = tuple slot 11).  The switch is a template parameter of the kernel itself: a shared __device__
+// body changes these kernels' instruction streams, template parameters on the kernel do not
+// (profiles/kernel_templates_refactor.md).  v_depth is always present (nullptr without DEPTH): one signature.
+template <bool STATE, bool DEPTH = false>
+__global__ __launch_bounds__(256) void raster_bwd_rs_kernel(
+    RasterParams prm, RsParams rs, const int* __restrict__ ids, const int* __restrict__ eids,
+    const float* __restrict__ records, unsigned max_id, const float* __restrict__ out_T,
+    const int* __restrict__ final_idx, const float* __restrict__ v_img, const float* __restrict__ v_alpha,
+    unsigned n_blocks, float* __restrict__ bwd_T, float* __restrict__ bwd_B, float* __restrict__ tuples,
+    unsigned char* __restrict__ flags, const float* __restrict__ v_depth) {
+  __shared__ __attribute__((aligned(16))) float lds_all[4 * rs_floats(DEPTH)];
+  const int lane = lane_id();
+  float* red = lds_all + (threadIdx.x >> 6) * rs_floats(DEPTH);
+  const int T = prm.tiles_x * prm.tiles_y;
+  const unsigned work = (unsigned)__builtin_amdgcn_readfirstlane(
+      (int)(xcd_remap(blockIdx.x, n_blocks) * 4u + (threadIdx.x >> 6)));
+  if (work >= (unsigned)(prm.S * T)) return;
+  const int s = work / T, t = work % T;
+  const int ty = t / prm.tiles_x, tx = t % prm.tiles_x;
+  const bool shared = rs.times != nullptr;
+  const float t_s = shared ? rs.times[s] : 0.f;
+  int2 range = prm.tile_bins[shared ? (size_t)t : (size_t)s * T + t];
+  range.x = __builtin_amdgcn_readfirstlane(range.x);
+  range.y = __builtin_amdgcn_readfirstlane(range.y);
+  if (range.y <= range.x) return;
+  // lane -> its four pixels, one per 8x8 quadrant: pixel k at (px0 + 8 (k & 1), py0 + 8 (k >> 1))
+  const int px0 = tx * K::kTile + (lane & 7);
+  const int py0 = ty * K::kTile + (lane >> 3);
+  const float pxf = (float)px0 + 0.5f;
+  const float bgr = prm.background[0], bgg = prm.background[1], bgb = prm.background[2];
+  RsQuad pp;
+  int my_end = range.x;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int x = px0 + 8 * (k & 1), y = py0 + 8 * (k >> 1);
+    float Tk = 1.f, Dv = 0.f, vr = 0.f, vg = 0.f, vb = 0.f, vd = 0.f;
+    int fin = range.x;
+    if (x < prm.W && y < prm.H) {
+      const size_t pix = ((size_t)s * prm.H + y) * prm.W + x;
+      const float Tfin = out_T[pix];
+      fin = min(max(final_idx[pix], range.x), range.y);      // a stop index never leaves the tile's list
+      if (DEPTH) vd = v_depth[pix];
+      vr = v_img[pix * 3 + 0]; vg = v_img[pix * 3 + 1]; vb = v_img[pix * 3 + 2];
+      if (prm.cmb_scale) {
+        const size_t q = ((size_t)y * prm.W + x) * 3;
+        vr = combine_grad(vr, prm.cmb_scale[q + 0], prm.cmb_gamma, prm.cmb_min);
+        vg = combine_grad(vg, prm.cmb_scale[q + 1], prm.cmb_gamma, prm.cmb_min);
+        vb = combine_grad(vb, prm.cmb_scale[q + 2], prm.cmb_gamma, prm.cmb_min);
+      }
+      const float va_out = v_alpha ? v_alpha[pix] : 0.f;
+      const float va = Tfin * (va_out - (bgr * vr + bgg * vg + bgb * vb));
+      Tk = Tfin;
+      Dv = -va;
+      if (STATE) { Tk = bwd_T[pix]; Dv = bwd_B[pix] - va; }
+    }
+    my_end = max(my_end, fin);
+    pp.T[k] = Tk; pp.Dv[k] = Dv; pp.vr[k] = vr; pp.vg[k] = vg; pp.vb[k] = vb; pp.py[k] = (float)y + 0.5f; pp.fin[k] = fin;
+    pp.vd[k] = vd;
+  }
+  pp.tau[0] = rs_tau((float)py0 + 0.5f, (float)prm.H, rs.rs_time, t_s);
+  pp.tau[1] = rs_tau((float)(py0 + 8) + 0.5f, (float)prm.H, rs.rs_time, t_s);
+  const int wave_end = __builtin_amdgcn_readfirstlane(wave_max_i(my_end));
+  const float agm = prm.alpha_grad_max;
+  const unsigned s_base = shared ? 0u : (unsigned)s * (unsigned)rs.N;
+  const unsigned max_g = (unsigned)(rs.N - 1);
+  // shared list: the S samples' waves write the SAME entry's gradients — every (entry, sample) pair gets a tuple of its
+  // own, e * S + s (the S tuples of an entry are adjacent, a Gaussian's tuples stay one contiguous range)
+  const unsigned tmul = shared ? (unsigned)prm.S : 1u, tofs = shared ? (unsigned)s : 0u;
+  const unsigned n = (unsigned)(wave_end - range.x);
+  if (n != 0u) {
+    constexpr int kRows = rs_comp(DEPTH);
+    const int row = lane;                                    // row-sum role: lanes 0..43 (0..47 with DEPTH)
+    const int row_g = row / kRows, row_c = row - row_g * kRows;   // row_c = tuple slot (DEPTH: 11 = d loss / d depth)
+    const int4* __restrict__ ids4 = reinterpret_cast<const int4*>(ids);
+    const int4* __restrict__ eids4 = reinterpret_cast<const int4*>(eids);
+    auto rec = [&](int id) {
+      const unsigned gi = min((unsigned)id, max_id);
+      return load_rs_b<DEPTH>(records, rs.pix_vel, gi, min(gi - s_base, max_g));
+    };
+    int b = (wave_end - 1) & ~3;
+    const int b_last = range.x & ~3;
+    int4 idv = ids4[b >> 2];
+    RsRecB a0 = rec(idv.w), a1 = rec(idv.z);
+    for (;;) {
+      // pair A (entries b+3, b+2) is ready; put pair B (b+1, b) and the indices of the next (lower) group in flight
+      asm volatile("" :: "s"(a0.x), "s"(a1.x), "s"(a0.pvx), "s"(a1.pvx) : "memory");
+      const RsRecB b0 = rec(idv.y), b1 = rec(idv.x);
+      const int4 ev = eids4[b >> 2];
+      idv = ids4[max(b - 4, 0) >> 2];
+      asm volatile("" ::: "memory");
+      unsigned filled = 0;
+      if ((unsigned)(b + 3 - range.x) < n && rs_bwd_entry<DEPTH>(a0, pxf, b + 3, pp, red, 3, lane, agm)) filled |= 8u;
+      if ((unsigned)(b + 2 - range.x) < n && rs_bwd_entry<DEPTH>(a1, pxf, b + 2, pp, red, 2, lane, agm)) filled |= 4u;
+      asm volatile("" :: "s"(b0.x), "s"(b1.x), "s"(b0.pvx), "s"(b1.pvx), "s"(idv.x), "s"(ev.x) : "memory");
+      a0 = rec(idv.w); a1 = rec(idv.z);
+      asm volatile("" ::: "memory");
+      if ((unsigned)(b + 1 - range.x) < n && rs_bwd_entry<DEPTH>(b0, pxf, b + 1, pp, red, 1, lane, agm)) filled |= 2u;
+      if ((unsigned)(b - range.x) < n && rs_bwd_entry<DEPTH>(b1, pxf, b, pp, red, 0, lane, agm)) filled |= 1u;
+      if (filled) {
+        __builtin_amdgcn_wave_barrier();
+        if (row < kRsGroup * kRows && ((filled >> row_g) & 1u)) {
+          const f4* rp = reinterpret_cast<const f4*>(red + row * kRsStride);
+          f4 s0 = rp[0], s1 = rp[1], s2 = rp[2], s3 = rp[3];
+          s0 += rp[4]; s1 += rp[5]; s2 += rp[6]; s3 += rp[7];
+          const f4 v = (s0 + s1) + (s2 + s3);
+          const float sum = (v.x + v.y) + (v.z + v.w);
+          const int id_e = row_g == 0 ? ev.x : (row_g == 1 ? ev.y : (row_g == 2 ? ev.z : ev.w));
+          const size_t e = (size_t)(unsigned)id_e * tmul + tofs;
+          tuples[e * kGradFloats + row_c] = sum;
+          if (row_c == 0) flags[e] = 2;                      // 2: slot 5 is the plain sum of v_sigma
+        }
+        __builtin_amdgcn_wave_barrier();
+      }
+      if (b <= b_last) break;
+      b -= 4;
+    }
+  }
+  if (STATE) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int x = px0 + 8 * (k & 1), y = py0 + 8 * (k >> 1);
+      if (x < prm.W && y < prm.H) {
+        const size_t pix = ((size_t)s * prm.H + y) * prm.W + x;
+        const float Tfin = out_T[pix];
+        const float va_out = v_alpha ? v_alpha[pix] : 0.f;
+        const float va = Tfin * (va_out - (bgr * pp.vr[k] + bgg * pp.vg[k] + bgb * pp.vb[k]));
+        bwd_T[pix] = pp.T[k];
+        bwd_B[pix] = pp.Dv[k] + va;
+      }
+    }
+  }
 }
-
-GS_BWD_RS_KERNEL(raster_bwd_rs_kernel, false, GS_RS_NO_DEPTH_PARAM, const float* const v_depth = nullptr; (void)v_depth;)
-GS_BWD_RS_KERNEL(raster_bwd_rs_depth_kernel, true, GS_RS_DEPTH_PARAM, )
 
 }  // namespace gs
 
@@ -578,15 +572,13 @@ extern "C" int gs_rasterize_bwd_rs_slice_depth(const float* records, const int* 
   if (variant & GS_VARIANT_CLAMP_GRAD) prm.alpha_grad_max = 3.0e38f;
   RsParams rs; rs.pix_vel = pix_vel; rs.N = N; rs.rs_time = rolling_shutter_time; rs.times = shared_list_times;
   const unsigned work = (unsigned)(S * prm.tiles_x * prm.tiles_y), blocks = (work + 3) / 4;
-  // <STATE> of one of the two families; bwd_T and bwd_B are both given or both NULL (checked above)
-  auto launch = [&](auto* k_state, auto* k_plain, auto... extra) {
-    hipLaunchKernelGGL(bwd_T ? k_state : k_plain, dim3(blocks), dim3(256), 0, (hipStream_t)stream, prm, rs, sorted_ids,
-                       sorted_vals, records, (unsigned)(n_records - 1), out_T, final_idx, v_img, v_alpha, blocks, bwd_T,
-                       bwd_B, tuples, flags, extra...);
-    return gs_launch_status();
-  };
-  if (v_depth) return launch(raster_bwd_rs_depth_kernel<true>, raster_bwd_rs_depth_kernel<false>, v_depth);
-  return launch(raster_bwd_rs_kernel<true>, raster_bwd_rs_kernel<false>);
+  // <STATE, DEPTH>; bwd_T and bwd_B are both given or both NULL (checked above)
+  const auto kernel = v_depth ? (bwd_T ? raster_bwd_rs_kernel<true, true> : raster_bwd_rs_kernel<false, true>)
+                              : (bwd_T ? raster_bwd_rs_kernel<true, false> : raster_bwd_rs_kernel<false, false>);
+  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, prm, rs, sorted_ids, sorted_vals, records,
+                     (unsigned)(n_records - 1), out_T, final_idx, v_img, v_alpha, blocks, bwd_T, bwd_B, tuples, flags,
+                     v_depth);
+  return gs_launch_status();
 }
 
 GS_EXPORT int gs_rasterize_bwd_rs_slice(const float* records, const int* sorted_vals, const int* tile_bins,

@@ -193,15 +193,16 @@ def test_twin_backend_raises_on_absgrad(gs, monkeypatch):
 # What the build produces (gfx950, the library's flags), rounded up to the 8-register allocation granule: the state-less
 # rgb forms 80, with reverse-traversal state 87 -> 88, the depth forms 85 -> 88 and 91 -> 96.  All inside the 96 that
 # five waves per SIMD allow (the launch bound of the default kernels, untouched), none spills a VGPR.
+# raster_bwd_sload_kernel<STATE, OUT, DEPTH, ABSGRAD, CAMS>: the ABSGRAD = true instantiations
 BUDGET = {
-    "raster_bwd_absgrad_kernel<false, 1>": 80,
-    "raster_bwd_absgrad_kernel<true, 1>": 88,
-    "raster_bwd_absgrad_cams_kernel<false, 1>": 80,
-    "raster_bwd_absgrad_cams_kernel<true, 1>": 88,
-    "raster_bwd_absgrad_depth_kernel<false, 1>": 88,
-    "raster_bwd_absgrad_depth_kernel<true, 1>": 96,
-    "raster_bwd_absgrad_depth_cams_kernel<false, 1>": 88,
-    "raster_bwd_absgrad_depth_cams_kernel<true, 1>": 96,
+    "raster_bwd_sload_kernel<false, 1, false, true, false>": 80,
+    "raster_bwd_sload_kernel<true, 1, false, true, false>": 88,
+    "raster_bwd_sload_kernel<false, 1, false, true, true>": 80,
+    "raster_bwd_sload_kernel<true, 1, false, true, true>": 88,
+    "raster_bwd_sload_kernel<false, 1, true, true, false>": 88,
+    "raster_bwd_sload_kernel<true, 1, true, true, false>": 96,
+    "raster_bwd_sload_kernel<false, 1, true, true, true>": 88,
+    "raster_bwd_sload_kernel<true, 1, true, true, true>": 96,
 }
 # LDS per block of four waves: 4 x 4 entries x (11 | 12) rows x 36 floats; five blocks per CU must fit into 160 KB
 LDS_BYTES = {False: 4 * 4 * 11 * 36 * 4, True: 4 * 4 * 12 * 36 * 4}
@@ -235,5 +236,5 @@ def test_absgrad_kernels_stay_inside_their_register_budgets(tmp_path):
         print(f"{frag}: {vgpr} VGPRs (budget {max_vgpr}), {spill} spilled, {lds} B LDS, {scratch} B scratch")
         assert vgpr <= max_vgpr <= 96, (frag, vgpr)
         assert spill == 0 and scratch == 0, (frag, spill, scratch)
-        assert lds == LDS_BYTES["depth" in frag], (frag, lds)
+        assert lds == LDS_BYTES[frag.split(", ")[2] == "true"], (frag, lds)      # DEPTH: the third template argument
         assert 5 * lds <= 160 * 1024

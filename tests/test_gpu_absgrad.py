@@ -249,6 +249,48 @@ def test_batch_rows_equal_single_camera_absgrad(gs, dev):
             assert float(a1.max()) > 0
 
 
+@pytest.mark.parametrize("depth", [False, True])
+def test_batch_absgrad_in_several_slices_matches_per_pair_reference(gs, oracle, dev, depth):
+    """a frame of two cameras (two samples each, 4 x 3 tiles) under a slice budget that forces several depth slices:
+    raster_bwd_sload_kernel<true, 1, DEPTH, true, true>.  Every camera's absgrad and xy_grad_out rows against the
+    per-pair reference of that camera alone, at the bar of test_absgrad_matches_per_pair_reference"""
+    from gsdeblur_amd import ops
+    from test_gpu_batch import _cameras, _viewmats, _args, G_NAMES
+    O = oracle
+    W, H, n, S, B = 64, 48, 400, 2, 2
+    sc = _scene(O, n, W, H, 41)
+    cams = _cameras(gs, sc, B, seed=1)
+    refs = []
+    for b, (V, lin, ang, et) in enumerate(cams):
+        sc_b = dict(sc, viewmat=V, lin_vel=lin, ang_vel=ang)
+        cfg = O.RenderConfig(H, W, sc["fx"], sc["fy"], sc["cx"], sc["cy"], blur_samples=S, rs_bands=1, exposure_time=et,
+                             rolling_shutter_time=1 / 30, gamma=2.2, min_rgb_level=10.0)
+        refs.append(_reference_with_depth(O, sc_b, cfg, True, 7 + b) if depth else _reference(O, sc_b, cfg, True, None, 7 + b))
+    p = {k: sc[k].float().to(dev).requires_grad_(True) for k in G_NAMES}
+    vms = torch.stack([_viewmats(gs, c, S, 1, dev) for c in cams])
+    xy = torch.zeros(B, n, 2, device=dev)
+    xa = torch.full((B, n, 2), float("nan"), device=dev)
+    old = ops.SLICE_BASE
+    try:
+        ops.SLICE_BASE = 2
+        res = gs.render_batch(*_args(p), vms, None, S, 1, sc["fx"], sc["fy"], sc["cx"], sc["cy"], H, W, gamma=2.2,
+                              min_rgb_level=10.0, xy_grad_out=xy, xy_absgrad_out=xa, return_depth=depth)
+        loss = sum((refs[b]["wc"].float().to(dev) * res[0][b]).sum() for b in range(B))
+        if depth:
+            loss = loss + sum((refs[b]["wd"].float().to(dev) * res[3][b]).sum() for b in range(B))
+        loss.backward()
+        torch.cuda.synchronize()
+        assert sum(1 for x in ops.last_slice_intersects if x > 0) >= 2
+    finally:
+        ops.SLICE_BASE = old
+    for b in range(B):
+        r_abs = grad_el_ratio(xa[b].cpu().numpy(), refs[b]["abs"].numpy())
+        r_sgn = grad_el_ratio(xy[b].cpu().numpy(), refs[b]["signed"].numpy())
+        print(f"camera {b}, depth={depth}: grad_el_ratio absgrad {r_abs:.3f}, signed {r_sgn:.3f}")
+        assert float(refs[b]["abs"].max()) > 0
+        assert r_abs <= 1.0 and r_sgn <= 1.0, (b, r_abs, r_sgn)
+
+
 @pytest.mark.parametrize("S,R,combined", [(1, 1, False), (5, 1, True)])
 def test_depth_and_absgrad_in_one_call(gs, oracle, dev, S, R, combined):
     """return_depth=True with a depth loss term: absgrad (of the whole loss, the depth as a fourth colour), xy_grad_out

@@ -97,10 +97,7 @@ def test_batch_forward_with_several_depth_slices(gs, dev):
         ops.SLICE_BASE = old
 
 
-@pytest.mark.parametrize("loss_kind,learn_bg", [("rgb", False), ("rgb+depth", False), ("rgb", True)])
-def test_batch_backward_matches_oracle(gs, oracle, dev, loss_kind, learn_bg):
-    O = oracle
-    W, H, n, S, R, B = 128, 96, 3000, 3, 2, 3
+def _backward_vs_oracle(gs, O, dev, loss_kind, learn_bg, W, H, n, S, R, B):
     sc = O.synthetic_scene(n, W, H, seed=41, scale_mult=6.0)
     sc["lin_vel"], sc["ang_vel"] = sc["lin_vel"] * 20, sc["ang_vel"] * 10
     cams = _cameras(gs, sc, B, seed=1)
@@ -155,6 +152,26 @@ def test_batch_backward_matches_oracle(gs, oracle, dev, loss_kind, learn_bg):
         ratios["background"] = grad_el_ratio(bg.grad.cpu().numpy(), qbg.grad.numpy())
     print("grad_el_ratio", ratios)
     assert max(ratios.values()) <= 1.0, ratios
+
+
+@pytest.mark.parametrize("loss_kind,learn_bg", [("rgb", False), ("rgb+depth", False), ("rgb", True)])
+def test_batch_backward_matches_oracle(gs, oracle, dev, loss_kind, learn_bg):
+    _backward_vs_oracle(gs, oracle, dev, loss_kind, learn_bg, W=128, H=96, n=3000, S=3, R=2, B=3)
+
+
+@pytest.mark.parametrize("loss_kind", ["rgb", "rgb+depth"])
+def test_batch_backward_in_several_slices_matches_oracle(gs, oracle, dev, loss_kind):
+    """a slice budget that forces several depth slices: the backward compositor of a frame of several cameras carries its
+    reverse-traversal state from slice to slice (raster_bwd_sload_kernel<true, 1, DEPTH, false, true>).  4 x 3 tiles, two
+    cameras of two samples each, so that the camera of sample image s is s / 2"""
+    from gsdeblur_amd import ops
+    old = ops.SLICE_BASE
+    try:
+        ops.SLICE_BASE = 2
+        _backward_vs_oracle(gs, oracle, dev, loss_kind, False, W=64, H=48, n=400, S=2, R=1, B=2)
+        assert sum(1 for x in ops.last_slice_intersects if x > 0) >= 2
+    finally:
+        ops.SLICE_BASE = old
 
 
 def _batch_grads(gs, dev, sc, cams, S, R, H, W, wc):

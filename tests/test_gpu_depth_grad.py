@@ -175,6 +175,19 @@ def test_pixel_velocity_depth_gradient_matches_oracle(gs, oracle, dev, case, los
     _compare(O, gs, dev, sc, cfg, S, R, "pixvel", False, 1.0, rs_time, shared, loss_kind, 11)
 
 
+def test_exact_rolling_shutter_depth_gradient_in_one_slice_matches_oracle(gs, oracle, dev):
+    """the cases above are frames of several depth slices; one of 4 x 3 tiles and 400 Gaussians fits into one, so the exact
+    rolling-shutter backward runs without reverse-traversal state (raster_bwd_rs_kernel<false, true>)"""
+    from gsdeblur_amd import ops
+    O = oracle
+    W, H, n, S = 64, 48, 400, 2
+    sc = _scene(O, n, W, H, 43)
+    cfg = O.RenderConfig(H, W, sc["fx"], sc["fy"], sc["cx"], sc["cy"], blur_samples=S, rs_bands=1, exposure_time=1 / 60,
+                         rolling_shutter_time=1 / 30, motion_model="pixel_velocity", rs_exact=True, shared_list=False)
+    _compare(O, gs, dev, sc, cfg, S, 1, "pixvel", False, 1.0, 1 / 30, False, "rgb+depth", 11)
+    assert sum(1 for x in ops.last_slice_intersects if x > 0) == 1
+
+
 def _frame_grads(gs, dev, sc, v_depth_scale, motion="se3", seed=3):
     """render_step of one frame with an rgb gradient and (v_depth_scale not None) a depth gradient; -> grads dict"""
     from gsdeblur_amd.step import render_step

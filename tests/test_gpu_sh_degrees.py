@@ -177,15 +177,15 @@ def test_other_routes_give_the_default_result_at_other_degrees(gs, oracle, dev, 
     atomics backward in test_tuple_backward_equals_atomic_backward, another slicing in
     test_depth_sliced_equals_single_pass), unused bands and unseen rows exact zeros on both.
       DEFER_COLOR=0  SH in the projection: project_fused_fwd_kernel<25,false> at (4,25), <16,false> with nb < K_stride at
-                     (3,25) / (1,16); its backward is project_fused_bwd_sparse_kernel<MAXB,true> through the Python
+                     (3,25) / (1,16); its backward is project_fused_bwd_sparse_kernel<MAXB,true,false> through the Python
                      orchestration
-      GRAD_TUPLES=0  fp32 atomics into v_records, no `touched` flags: the DENSE project_fused_bwd_kernel<25> at (4,25);
-                     at (3,25) project_fused_bwd_kernel<16> with K_stride 25, whose tail loop zeroes the bands the
+      GRAD_TUPLES=0  fp32 atomics into v_records, no `touched` flags: the DENSE project_fused_bwd_kernel<25,false> at
+                     (4,25); at (3,25) project_fused_bwd_kernel<16,false> with K_stride 25, whose tail loop zeroes the bands the
                      instantiation does not hold
       SLICE_BASE=4   several depth slices (asserted: >= 2 non-empty): gs_slice_colors (slice_colors_kernel<25> at
                      (4,25)) runs once per slice
-    The non-zero-fill forms project_fused_bwd_sparse_kernel<.,false> / _sparse_depth_kernel<.,false> and the dense
-    project_fused_bwd_depth_kernel have no caller in the Python package (ops passes the zero-fill flag whenever it has
+    The non-zero-fill forms project_fused_bwd_sparse_kernel<.,false,.> and the dense depth form
+    project_fused_bwd_kernel<.,true> have no caller in the Python package (ops passes the zero-fill flag whenever it has
     `touched` flags, and the frame backend without them has no depth channel): only a C caller reaches them."""
     from gsdeblur_amd import ops
     sc = C.scene(oracle, deg, K)
@@ -210,7 +210,7 @@ def test_other_routes_give_the_default_result_at_other_degrees(gs, oracle, dev, 
 
 
 def test_degree_4_depth_gradient_vs_oracle(gs, oracle, dev):
-    """return_depth=True with a depth term in the loss: project_fused_bwd_sparse_depth_kernel<25,true>, against the
+    """return_depth=True with a depth term in the loss: project_fused_bwd_sparse_kernel<25,true,true>, against the
     oracle's depth composite (test_gpu_depth_grad._oracle_depth), at the bars of part 1"""
     sc, f, wt, wd = _oracle_case(oracle, 4, 25, depth=True)
     for layout in ("single", "split"):
