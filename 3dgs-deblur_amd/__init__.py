@@ -26,7 +26,8 @@ from .ops import (  # noqa: F401
 )
 from .model import Camera, CameraShutterOptimizerConfig, SplatfactoDeblurConfig, SplatfactoDeblurModel  # noqa: F401
 from . import dp  # noqa: F401
-from . import bilagrid, checkpoint, data, densify, fused, mcmc, step, train_step as training  # noqa: F401
+from . import bilagrid, checkpoint, colorcorrect, data, densify, fused, mcmc, step, train_step as training  # noqa: F401
+from .colorcorrect import color_correct  # noqa: F401
 from .step import render_step  # noqa: F401
 from .data import load_transforms, load_seed_points_ply  # noqa: F401
 

@@ -284,7 +284,8 @@ def _restore_into(model: SplatfactoDeblurModel, sec: Dict) -> None:
     """the saved state into an existing model of the same config: the six Gaussian parameters are REPLACED by
     parameters of the saved row count, the small ones copied"""
     saved_cfg, own_cfg = config_to_dict(config_from_dict(sec["config"])), config_to_dict(model.config)
-    diff = sorted(k for k in saved_cfg if saved_cfg[k] != own_cfg.get(k))
+    # color_corrected_metrics only chooses what evaluate() reports: a run may be resumed with it switched either way
+    diff = sorted(k for k in saved_cfg if saved_cfg[k] != own_cfg.get(k) and k != "color_corrected_metrics")
     if diff:
         raise ValueError(f"the checkpoint's config differs from the model's in {diff}")
     if int(sec["num_cameras"]) != int(model.num_cameras):

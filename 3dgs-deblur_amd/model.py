@@ -104,6 +104,9 @@ class SplatfactoDeblurConfig:
     use_bilateral_grid: bool = False
     grid_shape: Tuple[int, int, int] = (16, 16, 8)     # (GW, GH, L)
     bilateral_grid_tv_lambda: float = 10.0             # weight of the total-variation penalty on all grids
+    # evaluation only (splatfacto's name): train_step.evaluate also reports cc_psnr / cc_ssim, taken after each render was
+    # fitted to its ground truth by a per-channel quadratic colour warp (colorcorrect.py).  False: same keys, same path
+    color_corrected_metrics: bool = False
 
 
 @dataclass

@@ -483,20 +483,39 @@ def eval_camera_step(model: SplatfactoDeblurModel, optimizers: Dict[str, torch.o
 
 
 @torch.no_grad()
-def evaluate(model: SplatfactoDeblurModel, cameras, images, indices, batch_size: int = 1) -> Dict[str, float]:
+def evaluate(model: SplatfactoDeblurModel, cameras, images, indices, batch_size: int = 1,
+             color_corrected: Optional[bool] = None) -> Dict[str, float]:
     """mean PSNR / SSIM of the model's renders of `indices` against their images (sharp frames in the synthetic sets).
-    batch_size > 1 renders up to that many cameras per call (model.get_outputs_for_cameras)"""
-    ps, ss = [], []
+    batch_size > 1 renders up to that many cameras per call (model.get_outputs_for_cameras).  color_corrected (None:
+    model.config.color_corrected_metrics): the result gains cc_psnr / cc_ssim, the same two metrics of each render
+    (clamped to [0,1]) after colorcorrect.color_correct fitted it to its image — one call per render batch; psnr and ssim
+    stay what they are without it"""
+    if color_corrected is None:
+        color_corrected = bool(model.config.color_corrected_metrics)
+    ps, ss, cps, css = [], [], [], []
     indices = list(indices)
+    if color_corrected:
+        from .colorcorrect import color_correct
     if batch_size > 1:
-        rgbs = []
+        rgbs, fitted = [], []
         for k in range(0, len(indices), batch_size):
-            rgbs += list(model.get_outputs_for_cameras([cameras[i] for i in indices[k:k + batch_size]])["rgb"])
+            ids = indices[k:k + batch_size]
+            batch = model.get_outputs_for_cameras([cameras[i] for i in ids])["rgb"]
+            rgbs += list(batch)
+            if color_corrected:
+                fitted += list(color_correct(batch.clamp(0, 1), torch.stack([images[i] for i in ids])))
     for n, i in enumerate(indices):
         rgb = rgbs[n] if batch_size > 1 else model.get_outputs_for_camera(cameras[i])["rgb"]
         ps.append(psnr(rgb, images[i]))
         ss.append(float(ssim(rgb.clamp(0, 1), images[i]).item()))
-    return {"psnr": sum(ps) / max(1, len(ps)), "ssim": sum(ss) / max(1, len(ss))}
+        if color_corrected:
+            cc = fitted[n] if batch_size > 1 else color_correct(rgb.clamp(0, 1), images[i])
+            cps.append(psnr(cc, images[i]))
+            css.append(float(ssim(cc, images[i]).item()))
+    res = {"psnr": sum(ps) / max(1, len(ps)), "ssim": sum(ss) / max(1, len(ss))}
+    if color_corrected:
+        res.update(cc_psnr=sum(cps) / max(1, len(cps)), cc_ssim=sum(css) / max(1, len(css)))
+    return res
 
 
 def train_scene(model: SplatfactoDeblurModel, scene, images, iterations: int, lr_scale: float = 1.0,
@@ -506,7 +525,8 @@ def train_scene(model: SplatfactoDeblurModel, scene, images, iterations: int, lr
                 resume=None) -> Dict:
     """Train on scene.train_indices (one view per step, seeded shuffle), optionally refining the evaluation cameras
     in between; returns {'results': {psnr, ssim}, 'wall_clock_time_seconds', 'history'} like the reference's
-    metrics.json (/root/reference/train.py:87-100, parse_outputs.py:58).  depths (optional): per-frame depth maps
+    metrics.json (/root/reference/train.py:87-100, parse_outputs.py:58); with config.color_corrected_metrics the results
+    also carry cc_psnr / cc_ssim (evaluate).  depths (optional): per-frame depth maps
     [H,W,1] or None, indexed like images (data.load_depth); with depth_lambda > 0 every step adds the depth loss.
     batch_size > 1: every step takes that many views of the shuffle (fewer at the end of a pass) as one batch
     (train_step with lists), and the evaluation renders in batches of that size.  optimizer: make_optimizers' choice

@@ -797,6 +797,23 @@ long long gs_bilagrid_tv_workspace_bytes(int G, int GW, int GH, int L);
 int gs_bilagrid_tv_fwd_bwd(int G, int GW, int GH, int L, const float* grids, float weight, float* loss_out,
                            float* v_grids, void* ws, long long ws_bytes, void* stream);
 
+/* ---- colour-corrected evaluation metrics (mip-NeRF 360's color_correct as in gsplat's lib_bilagrid / nerfstudio
+ * splatfacto's color_corrected_metrics, recollected; csrc/colorcorrect_math.h states the algorithm): colorcorrect.py drives
+ * it.  No allocation, no state, no float atomics: every sum is float64 in an order fixed by (H, W), so two runs agree bit
+ * for bit and an image's result does not depend on the rest of the batch.
+ *
+ * img, ref, out [B,H,W,3] fp32 (out neither img nor ref).  Each of the B pairs is fitted on its own: num_iters times, per
+ * output channel c the quadratic warp w_c of the features (rr, rg, rb, gg, gb, bb, r, g, b, 1) that minimises the squared
+ * error to ref[c] over the pixels whose img[c], current x[c] and ref[c] all lie in [float(eps), float(1 - eps)]; then x <-
+ * clip(a . w, 0, 1) for every pixel, stored as fp32.  A channel with fewer than 10 such pixels or a numerically
+ * rank-deficient normal matrix keeps the identity warp for that iteration.  out = x after the last iteration (num_iters
+ * == 0: a copy of img).  warps (NULL: not wanted) double [B,num_iters,3,10] receives every fitted warp.  ws: 8-byte
+ * aligned, gs_color_correct_workspace_bytes(B, H, W) bytes (-1 on invalid arguments; 1.6 MB per 1080p image).  All
+ * iterations run in this one call, nothing is read back.  B == 0 is a no-op; H * W <= 2^30, B <= 65535. */
+long long gs_color_correct_workspace_bytes(int B, int H, int W);
+int gs_color_correct(int B, int H, int W, const float* img, const float* ref, int num_iters, double eps, float* out,
+                     double* warps, void* ws, long long ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

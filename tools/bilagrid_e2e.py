@@ -1,7 +1,8 @@
 """End-to-end check of the bilateral-grid colour correction: the self-generated blurred dataset of tools/densify_e2e.py
 with every TRAINING image multiplied by a seeded per-image, per-channel gain (what auto-exposure and auto-white-balance
 do to handheld video); the evaluation images are left untouched.  Trained with and without the grid, and once on the
-unperturbed images for scale.  Sharp-frame PSNR / SSIM of the UNCORRECTED evaluation renders and the training seconds.
+unperturbed images for scale.  Sharp-frame PSNR / SSIM of the UNCORRECTED evaluation renders, the same two metrics after
+the colour fit of gs.color_correct (cc_psnr / cc_ssim; evaluation happens after the clock stops) and the training seconds.
 One scene, one seed.
 usage: python tools/bilagrid_e2e.py [iterations] [--record]   (--record appends the result to profiles/bilagrid_train.jsonl)"""
 import json
@@ -36,10 +37,11 @@ for name, images, grid in (("clean_images", clean, False), ("gains_no_grid", per
                            ("gains_with_grid", perturbed, True)):
     cfg = gs.SplatfactoDeblurConfig(sh_degree=3, blur_samples=5, gamma=2.2, min_rgb_level=0.0,
                                     rolling_shutter_compensation=False, use_scale_regularization=True,
-                                    use_bilateral_grid=grid)
+                                    use_bilateral_grid=grid, color_corrected_metrics=True)
     model = SD.init_from_seed_points(cfg, xyz, rgb, dev, num_cameras=len(scene.cameras))
     r = gs.training.train_scene(model, scene, images, iters)
     res[name] = {"psnr": round(r["results"]["psnr"], 3), "ssim": round(r["results"]["ssim"], 4),
+                 "cc_psnr": round(r["results"]["cc_psnr"], 3), "cc_ssim": round(r["results"]["cc_ssim"], 4),
                  "seconds": round(r["wall_clock_time_seconds"], 2)}
     if grid:
         dev_from_identity = (model.bilateral_grids.detach() - gs.bilagrid.identity_grids(1).to(dev)).abs().flatten(1).max(1)[0]

@@ -9,8 +9,9 @@ tools/train_deblur.py leaves as checkpoint_<name>.pt) or from a Gaussian-splat P
 For every image of the set: camera.metadata["cam_idx"] is set to the image's index (it selects the pose / velocity
 adjustment a checkpoint carries), model.get_outputs_for_camera renders it, and <stem>_pred.png, <stem>_gt.png and
 pred/depth/raw/<stem>.npy are written (the reference's names, render_model.py:101-104, 127-133).  metrics.json holds
-{"results": {"psnr", "ssim"}} with training.evaluate's formulas.  A PLY carries no camera-side parameters and no training
-config: it renders with the defaults at the file's SH degree and --blur-samples (default 0: one sharp render)."""
+{"results": {"psnr", "ssim"}} with training.evaluate's formulas; --color-correct adds <stem>_cc.png (the render after
+gs.color_correct fitted its colours to the image) and cc_psnr / cc_ssim.  A PLY carries no camera-side parameters and no
+training config: it renders with the defaults at the file's SH degree and --blur-samples (default 0: one sharp render)."""
 import argparse
 import json
 import os
@@ -34,6 +35,9 @@ def main():
     ap.add_argument("--out", required=True)
     ap.add_argument("--blur-samples", type=int, default=0, help="--ply only: blur samples of the render")
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--color-correct", action="store_true",
+                    help="also write <stem>_cc.png, the render fitted to its image by gs.color_correct, and cc_psnr / "
+                         "cc_ssim into metrics.json")
     args = ap.parse_args()
     dev = torch.device(args.device)
     scene = gs.load_transforms(args.data)
@@ -47,7 +51,7 @@ def main():
         model = gs.SplatfactoDeblurModel.from_ply(args.ply, cfg, dev, num_cameras=len(scene.cameras))
     indices = scene.eval_indices if args.set == "eval" else scene.train_indices
     os.makedirs(os.path.join(args.out, "pred", "depth", "raw"), exist_ok=True)
-    ps, ss = [], []
+    ps, ss, cps, css = [], [], [], []
     for i in indices:
         camera = scene.cameras[i]
         camera.metadata["cam_idx"] = i
@@ -59,7 +63,14 @@ def main():
         np.save(os.path.join(args.out, "pred", "depth", "raw", f"{stem}.npy"), depth.detach().cpu().numpy())
         ps.append(gs.training.psnr(rgb, images[i]))
         ss.append(float(gs.training.ssim(rgb.clamp(0, 1), images[i]).item()))
+        if args.color_correct:
+            cc = gs.color_correct(rgb.clamp(0, 1), images[i])
+            gs.data.save_image(os.path.join(args.out, f"{stem}_cc.png"), cc)
+            cps.append(gs.training.psnr(cc, images[i]))
+            css.append(float(gs.training.ssim(cc, images[i]).item()))
     results = {"psnr": sum(ps) / max(1, len(ps)), "ssim": sum(ss) / max(1, len(ss))}
+    if args.color_correct:
+        results.update(cc_psnr=sum(cps) / max(1, len(cps)), cc_ssim=sum(css) / max(1, len(css)))
     with open(os.path.join(args.out, "metrics.json"), "wt") as f:
         json.dump({"results": results, "set": args.set, "images": len(indices)}, f)
     print(json.dumps(results))

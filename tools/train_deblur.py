@@ -9,7 +9,8 @@ Variants follow /root/reference/train.py:29-76: blur_samples 0 = no motion-blur 
 5 (the default, train.py:46) and 10 (synthetic sets, train.py:22); --motion-model picks the SE(3) re-projection
 (north_star) or the paper's pixel-velocity model; --optimize-eval-cameras refines the evaluation poses without
 touching the Gaussians (train.py:180-183); --densify adds splatfacto's refinement schedule or 3DGS-MCMC (--cap-max);
---bilateral-grid learns a per-image colour correction with the scene; --optimize-exposure / --optimize-readout learn the
+--bilateral-grid learns a per-image colour correction with the scene; --color-corrected-metrics adds cc_psnr / cc_ssim
+(the evaluation renders fitted to their images by a quadratic colour warp first); --optimize-exposure / --optimize-readout learn the
 exposure and rolling-shutter readout times from their metadata values.  Every variant leaves checkpoint_<name>.pt beside
 its metrics_<name>.json (--checkpoint-every K: also every K steps; --resume PATH continues from one; --export-ply adds
 splat_<name>.ply for a viewer); tools/render_model.py renders either file."""
@@ -55,6 +56,9 @@ def main():
     ap.add_argument("--bilateral-grid", action="store_true",
                     help="per-image bilateral-grid colour correction of the training renders (exposure / white-balance "
                          "drift); evaluation renders are never corrected")
+    ap.add_argument("--color-corrected-metrics", action="store_true",
+                    help="also report cc_psnr / cc_ssim: the metrics after each evaluation render was fitted to its image "
+                         "by a per-channel quadratic colour warp (gs.color_correct)")
     ap.add_argument("--optimize-exposure", default=None, choices=["global", "per_camera"],
                     help="learn the exposure time (one log-scale adjustment for the scene, or one per training camera) "
                          "from the metadata value; SE(3) motion model only")
@@ -94,7 +98,8 @@ def main():
                                         rs_bands=min(8, (scene.cameras[0].height + 15) // 16),
                                         motion_model=args.motion_model, use_scale_regularization=True,
                                         optimizer=args.optimizer, selective_mask=args.selective_mask,
-                                        use_bilateral_grid=args.bilateral_grid)
+                                        use_bilateral_grid=args.bilateral_grid,
+                                        color_corrected_metrics=args.color_corrected_metrics)
         dcfg = None
         if args.densify == "splatfacto":
             dcfg = gs.densify.DensifyConfig(stop_split_at=int(0.7 * args.iterations),
