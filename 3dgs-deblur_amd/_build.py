@@ -29,6 +29,8 @@ SOURCES = [
     ("mcmc.hip", []),            # 3DGS-MCMC: per-step position noise, relocation correction (mcmc.py)
     ("bilagrid.hip", []),        # bilateral-grid colour correction: slice fwd / bwd, TV penalty (bilagrid.py)
     ("colorcorrect.hip", []),    # colour-corrected evaluation metrics: quadratic colour fit (colorcorrect.py)
+    # exact k nearest neighbours (knn.py): distances round every operation, as torch's and the host build's do
+    ("knn.hip", ["-ffp-contract=off"]),
     ("frame.hip", []),           # host-side frame orchestration (no kernels of its own)
 ]
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-fvisibility=hidden"]

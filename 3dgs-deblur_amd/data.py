@@ -326,9 +326,26 @@ def write_transforms(root: str, width: int, height: int, fx: float, fy: float, c
     return out
 
 
-def write_seed_points_ply(path: str, xyz: torch.Tensor, rgb: torch.Tensor) -> None:
-    """ASCII PLY `x y z red green blue` like /root/reference/process_synthetic_inputs.py:203-219"""
+def write_seed_points_ply(path: str, xyz: torch.Tensor, rgb: torch.Tensor, binary: bool = False) -> None:
+    """ASCII PLY `x y z red green blue` like /root/reference/process_synthetic_inputs.py:203-219; binary: the same columns
+    as binary_little_endian 1.0 (what COLMAP, Open3D and MeshLab write), the coordinates as full float32"""
     n = xyz.shape[0]
+    if binary:
+        import numpy as np
+        rows = np.zeros(n, dtype=np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"),
+                                           ("blue", "u1")]))
+        c = (rgb.clamp(0, 1) * 255.0 + 0.5).to(torch.int64).clamp(max=255).numpy()
+        for j, name in enumerate(("x", "y", "z")):
+            rows[name] = xyz[:, j].detach().cpu().float().numpy()
+        for j, name in enumerate(("red", "green", "blue")):
+            rows[name] = c[:, j]
+        header = "\n".join(["ply", "format binary_little_endian 1.0", f"element vertex {n}", "property float x",
+                            "property float y", "property float z", "property uchar red", "property uchar green",
+                            "property uchar blue", "end_header"]) + "\n"
+        with open(path, "wb") as f:
+            f.write(header.encode("ascii"))
+            f.write(rows.tobytes())
+        return
     lines = ["ply", "format ascii 1.0", f"element vertex {n}", "property float x", "property float y",
              "property float z", "property uint8 red", "property uint8 green", "property uint8 blue", "end_header"]
     c = (rgb.clamp(0, 1) * 255.0 + 0.5).to(torch.int64)
@@ -339,9 +356,64 @@ def write_seed_points_ply(path: str, xyz: torch.Tensor, rgb: torch.Tensor) -> No
         f.write("\n".join(lines) + "\n")
 
 
+def _load_seed_points_binary(raw: bytes, header_end: int, header: List[str]) -> Tuple[torch.Tensor, torch.Tensor]:
+    """the vertex element of a binary_little_endian PLY: columns found by name, other scalar columns skipped"""
+    import numpy as np
+    from .checkpoint import _PLY_TYPES
+    n, fields, element = None, [], None
+    for ln in header[1:]:
+        t = ln.split()
+        if not t or t[0] in ("comment", "obj_info"):
+            continue
+        if t[0] == "element":
+            if len(t) != 3:
+                raise ValueError(f"malformed PLY header line {ln!r}")
+            if n is None and t[1] != "vertex":
+                raise ValueError(f"PLY element {t[1]!r} stands before the vertex element")
+            element = t[1]
+            if element == "vertex":
+                n = int(t[2])
+        elif t[0] == "property" and element == "vertex":
+            if len(t) != 3 or t[1] not in _PLY_TYPES:
+                raise ValueError(f"vertex property {ln!r}: only scalar properties of the standard PLY types are read")
+            fields.append((t[2], "<" + _PLY_TYPES[t[1]]))
+    if n is None:
+        raise ValueError("PLY without a vertex element")
+    names = [nm for nm, _ in fields]
+    if len(set(names)) != len(names):
+        raise ValueError("PLY with a repeated vertex property name")
+    missing = [p for p in ("x", "y", "z") if p not in names]
+    if missing:
+        raise ValueError(f"PLY seed cloud misses the properties {missing}")
+    dtype = np.dtype(fields)
+    body = raw[header_end:]
+    if len(body) < n * dtype.itemsize:
+        raise ValueError(f"truncated PLY body: {len(body)} bytes for {n} rows of {dtype.itemsize}")
+    rows = np.frombuffer(body, dtype=dtype, count=n)
+
+    def take(cols):
+        return torch.from_numpy(np.stack([rows[c].astype(np.float32) for c in cols], axis=1)).reshape(n, 3)
+    has_rgb = all(c in names for c in ("red", "green", "blue"))
+    rgb = take(["red", "green", "blue"]) / 255.0 if has_rgb else torch.full((n, 3), 0.5)
+    return take(["x", "y", "z"]), rgb
+
+
 def load_seed_points_ply(path: str) -> Tuple[torch.Tensor, torch.Tensor]:
-    """ASCII PLY seed cloud `x y z red green blue` (/root/reference/process_synthetic_inputs.py:203-219)
-    -> (xyz [N,3] float32, rgb [N,3] float32 in 0..1)."""
+    """PLY seed cloud `x y z red green blue` -> (xyz [N,3] float32, rgb [N,3] float32 in 0..1): ASCII
+    (/root/reference/process_synthetic_inputs.py:203-219) or binary_little_endian 1.0 (COLMAP, Open3D, MeshLab), where the
+    columns are found by name, other scalar columns are skipped and a list property of the vertex element is a
+    ValueError."""
+    import re
+    with open(path, "rb") as f:
+        raw = f.read()
+    m = re.search(rb"end_header[ \t]*\r?\n", raw)
+    if raw.startswith(b"ply") and m is not None:
+        header = raw[:m.start()].decode("ascii", errors="replace").splitlines()
+        fmt = next((ln.split()[1:] for ln in header if ln.split()[:1] == ["format"]), None)
+        if fmt and fmt[0] == "binary_little_endian":
+            return _load_seed_points_binary(raw, m.end(), header)
+        if fmt and fmt[0] != "ascii":
+            raise ValueError(f"PLY format {fmt[0]!r}: seed clouds are read as ascii or binary_little_endian")
     with open(path, "rt") as f:
         lines = f.read().splitlines()
     if not lines or lines[0].strip() != "ply":

@@ -35,6 +35,7 @@ class CameraVelocityOptimizerConfig:
     zero_initial_velocities: bool = False  # train.py:70
 
 
+SH_C0 = 0.28209479177387814           # the SH band-0 basis value: colour = 0.5 + SH_C0 * sh[0]
 SHUTTER_EXPOSURE_MODES = ("off", "global", "per_camera")
 SHUTTER_READOUT_MODES = ("off", "global")
 
@@ -720,6 +721,39 @@ class SplatfactoDeblurModel(nn.Module):
         m = SplatfactoDeblurModel(config, scene["means"], scene["log_scales"], scene["quats"],
                                   scene["opacity_logits"], sh[:, 0, :], sh[:, 1:, :], num_cameras)
         return m.to(device)
+
+    @staticmethod
+    def from_seed_points(config: SplatfactoDeblurConfig, xyz: Tensor, rgb: Tensor, device, num_cameras: int = 1,
+                         seed: int = 0, min_scale: float = 1e-4):
+        """splatfacto's initialisation from a seed cloud (xyz [N,3], rgb [N,3] in 0..1; e.g. data.load_seed_points_ply):
+        isotropic scale = the mean distance to the 3 nearest neighbours, clamped to min_scale; random unit quaternions from
+        torch.Generator().manual_seed(seed); opacity 0.1; colour -> SH dc.  The neighbour search (knn.py) runs on
+        `device` and is linear in memory, so the cloud of a real capture (10^5..10^6 points) fits."""
+        import math
+        from .knn import knn_mean_distance
+        xyz = xyz.detach().to(torch.float32).cpu().contiguous()
+        n = int(xyz.shape[0])
+        g = torch.Generator().manual_seed(seed)
+        mean_d = knn_mean_distance(xyz.to(device), 3).cpu()
+        log_scales = torch.log(mean_d.clamp(min=min_scale))[:, None].repeat(1, 3)
+        quats = torch.randn(n, 4, generator=g)
+        quats = quats / quats.norm(dim=-1, keepdim=True)
+        sh = torch.zeros(n, (config.sh_degree + 1) ** 2, 3)
+        sh[:, 0, :] = (rgb.detach().cpu() - 0.5) / SH_C0
+        scene = dict(means=xyz.clone(), log_scales=log_scales, quats=quats,
+                     opacity_logits=torch.full((n,), math.log(0.1 / 0.9)), sh=sh)
+        return SplatfactoDeblurModel.from_scene(config, scene, device, num_cameras=num_cameras)
+
+    @staticmethod
+    def from_random(config: SplatfactoDeblurConfig, device, num_points: int = 50000, scale: float = 10.0,
+                    num_cameras: int = 1, seed: int = 0):
+        """splatfacto's random start (random_init / num_random / random_scale) for a scene without a seed cloud: means
+        uniform in the cube of side `scale` about the origin, uniform colours, the rest as from_seed_points; every draw
+        comes from torch.Generator().manual_seed(seed)"""
+        g = torch.Generator().manual_seed(seed)
+        xyz = (torch.rand(num_points, 3, generator=g) - 0.5) * scale
+        rgb = torch.rand(num_points, 3, generator=g)
+        return SplatfactoDeblurModel.from_seed_points(config, xyz, rgb, device, num_cameras=num_cameras, seed=seed)
 
     @staticmethod
     def from_ply(path, config: Optional[SplatfactoDeblurConfig] = None, device="cpu", num_cameras: int = 1):

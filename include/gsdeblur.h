@@ -814,6 +814,23 @@ long long gs_color_correct_workspace_bytes(int B, int H, int W);
 int gs_color_correct(int B, int H, int W, const float* img, const float* ref, int num_iters, double eps, float* out,
                      double* warps, void* ws, long long ws_bytes, void* stream);
 
+/* ---- exact k nearest neighbours of a point cloud against itself (csrc/knn_math.h states the algorithm and why it is
+ * exact; knn.py drives it): the scale of a Gaussian started from a seed cloud is the mean distance to its 3 nearest
+ * neighbours.  No allocation, no state, no float atomics; memory is linear in N.
+ *
+ * xyz [N,3] fp32, finite.  For every row i: the k smallest (squared distance, index) pairs over the rows j != i, a row
+ * excluded by index (a duplicate point is a neighbour at distance 0); d2 = (dx*dx + dy*dy) + dz*dz with dx = x_i - x_j in
+ * fp32 without fused multiply-add.  dists [N,k] receives the square roots, ascending; idx [N,k] (NULL: not wanted) the
+ * rows.  The values do not depend on the order of the rows or on scheduling.  1 <= k <= 16, k < N <= 2^26.
+ * cell_size <= 0: chosen on the device (twice the median k-th neighbour distance of <= 1024 fixed-stride rows); either
+ * way at least extent / 2^21.  max_rings <= 0: 8.  Rows still open after max_rings shells of the hashed grid are resolved
+ * by brute force.  stats (device, NULL: not wanted) receives 4 ints: the cell size (fp32 bits), max_rings, the number of
+ * brute-force rows, log2 of the bucket count.  ws: 256-byte aligned, gs_knn_workspace_bytes(N, k) bytes (-1 on invalid
+ * arguments; 60 to 80 bytes per row).  Everything runs in this one call, nothing is read back. */
+long long gs_knn_workspace_bytes(int N, int k);
+int gs_knn(int N, const float* xyz, int k, float cell_size, int max_rings, float* dists, int* idx, int* stats, void* ws,
+           long long ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

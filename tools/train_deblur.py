@@ -70,6 +70,10 @@ def main():
                     help="continue from a checkpoint: a file (one --blur-samples value), or a directory holding "
                          "checkpoint_<name>.pt for every variant of the run; --iterations stays the total")
     ap.add_argument("--export-ply", action="store_true", help="write splat_<name>.ply (Gaussian-splat PLY) per variant")
+    ap.add_argument("--random-init", type=int, default=0, metavar="N",
+                    help="start from N random Gaussians (splatfacto's random_init) instead of the dataset's seed cloud: "
+                         "for scenes without one")
+    ap.add_argument("--random-scale", type=float, default=10.0, help="--random-init: side of the cube the means are drawn in")
     ap.add_argument("--out", default="gpurun_out/deblur")
     args = ap.parse_args()
     if args.resume and not os.path.isdir(args.resume) and len(args.blur_samples) != 1:
@@ -82,7 +86,10 @@ def main():
                     rolling_shutter_time=args.rolling_shutter_time)
     scene = gs.load_transforms(root)
     images = gs.data.load_scene_images(scene, dev)          # undistorts when the scene carries lens coefficients
-    xyz, rgb = gs.load_seed_points_ply(scene.ply_file_path)
+    if args.random_init <= 0:
+        if not scene.ply_file_path:
+            ap.error("the dataset names no seed cloud (ply_file_path): give --random-init N")
+        xyz, rgb = gs.load_seed_points_ply(scene.ply_file_path)      # ASCII or binary little endian
     if args.pose_noise > 0:
         g = torch.Generator().manual_seed(3)
         for i in scene.eval_indices:
@@ -113,7 +120,12 @@ def main():
             cfg.camera_shutter_optimizer.exposure = args.optimize_exposure
         if args.optimize_readout:
             cfg.camera_shutter_optimizer.readout = "global"
-        model = SD.init_from_seed_points(cfg, xyz, rgb, dev, num_cameras=len(scene.cameras))
+        if args.random_init > 0:
+            model = gs.SplatfactoDeblurModel.from_random(cfg, dev, num_points=args.random_init, scale=args.random_scale,
+                                                         num_cameras=len(scene.cameras))
+        else:
+            # the neighbour search behind the initial scales runs on the GPU and is linear in memory (gs.knn)
+            model = gs.SplatfactoDeblurModel.from_seed_points(cfg, xyz, rgb, dev, num_cameras=len(scene.cameras))
         name = (f"blur_samples_{bs}" + ("_pixvel" if args.motion_model == "pixel_velocity" else "") +
                 ("" if args.rolling_shutter_time <= 0 else f"_rs_{args.rolling_shutter_mode}"))
         resume = args.resume
