@@ -31,6 +31,8 @@ SOURCES = [
     ("colorcorrect.hip", []),    # colour-corrected evaluation metrics: quadratic colour fit (colorcorrect.py)
     # exact k nearest neighbours (knn.py): distances round every operation, as torch's and the host build's do
     ("knn.hip", ["-ffp-contract=off"]),
+    # per-frame blur statistics (blurscore.py): per-pair values round every operation, as the host build's do
+    ("blur.hip", ["-ffp-contract=off"]),
     ("frame.hip", []),           # host-side frame orchestration (no kernels of its own)
 ]
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-fvisibility=hidden"]

@@ -106,6 +106,8 @@ _SIGS = {
     "gs_bilagrid_tv_fwd_bwd": [_I, _I, _I, _I, _P, _F, _P, _P, _P, _L, _P],
     "gs_color_correct": [_I, _I, _I, _P, _P, _I, ctypes.c_double, _P, _P, _P, _L, _P],
     "gs_knn": [_I, _P, _I, _F, _I, _P, _P, _P, _P, _L, _P],
+    "gs_blur_stats": [_I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _F, _P, _P, _P, _L, _P],
+    "gs_blur_stats_ppt": [_I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _F, _I, _P, _P, _P, _L, _P],
 }
 _SIGS_LL = {
     "gs_scan_workspace_bytes": [_L],
@@ -121,6 +123,7 @@ _SIGS_LL = {
     "gs_bilagrid_tv_workspace_bytes": [_I, _I, _I, _I],
     "gs_color_correct_workspace_bytes": [_I, _I, _I],
     "gs_knn_workspace_bytes": [_I, _I],
+    "gs_blur_stats_workspace_bytes": [_I, _I],
 }
 
 _lib = None

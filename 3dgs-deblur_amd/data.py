@@ -12,7 +12,9 @@
   eval split  "interval": sorted index i % 8 == 0 (/root/reference/train.py:174-177,
               /root/reference/process_synthetic_inputs.py:287-293); "filename": eval_/train_ prefixes
               (/root/reference/train_eval_split_by_blur_score.py:34-37, /root/reference/train.py:169-172);
-              "all" (/root/reference/train.py:164-167)
+              "all" (/root/reference/train.py:164-167); "blur_score": the sharpest frame of every run of 8 by
+              motion_blur_score, the split /root/reference/train_eval_split_by_blur_score.py:27-47 writes into file names
+              (write_blur_scored writes that dataset; blur_scores computes the score the reference takes from sai-cli)
 Host code (json + torch tensors); `load_image` decodes the frames (PNG / JPEG through PIL, or .npy float arrays)
 and `write_transforms` / `write_seed_points_ply` emit the same wire format (used by the self-generated datasets of
 ``tools/synthetic_dataset.py``, the offline stand-in for the Zenodo downloads of /root/reference/download_data.py:21-33).
@@ -45,8 +47,12 @@ class TransformsScene:
     depth_unit_scale_factor: float = 1e-3
 
 
-def split_indices(file_paths: List[str], eval_mode: str = "interval", eval_interval: int = 8) -> Tuple[List[int], List[int]]:
-    """(train, eval) indices into the path-sorted frame list."""
+def split_indices(file_paths: List[str], eval_mode: str = "interval", eval_interval: int = 8,
+                  scores: Optional[List[float]] = None) -> Tuple[List[int], List[int]]:
+    """(train, eval) indices into the path-sorted frame list.  eval_mode "blur_score" (the rule of
+    /root/reference/train_eval_split_by_blur_score.py:27-47) cuts the frames into runs of eval_interval — the last may be
+    shorter — and takes the frame with the smallest of `scores` (one per frame, in the same order) in each run for
+    evaluation, the first of them on a tie; the others train."""
     n = len(file_paths)
     if eval_mode == "all":
         return list(range(n)), list(range(n))
@@ -59,6 +65,14 @@ def split_indices(file_paths: List[str], eval_mode: str = "interval", eval_inter
         if not ev and not tr:
             raise ValueError("eval_mode='filename' needs eval_/train_ prefixed file names")
         return tr, ev
+    if eval_mode == "blur_score":
+        if scores is None or len(scores) != n:
+            raise ValueError("eval_mode='blur_score' needs one score per frame")
+        if int(eval_interval) < 1:
+            raise ValueError("eval_interval must be at least 1")
+        ev = [min(range(lo, min(n, lo + eval_interval)), key=lambda i: scores[i]) for lo in range(0, n, eval_interval)]
+        chosen = set(ev)
+        return [i for i in range(n) if i not in chosen], ev
     raise ValueError(f"unknown eval_mode {eval_mode!r}")
 
 
@@ -79,7 +93,14 @@ def load_transforms(path: str, eval_mode: str = "interval", eval_interval: int =
     W, H = int(round(meta["w"] * s)), int(round(meta["h"] * s))
     cams, paths, dpaths = [], [], []
     is_eval_set = set()
-    tr, ev = split_indices([fr["file_path"] for fr in frames], eval_mode, eval_interval)
+    scores = None
+    if eval_mode == "blur_score":
+        missing = [fr["file_path"] for fr in frames if "motion_blur_score" not in fr]
+        if missing:
+            raise ValueError(f"eval_mode='blur_score': {len(missing)} frames carry no motion_blur_score (first: "
+                             f"{missing[0]}); tools/blur_score.py --write-scores computes them")
+        scores = [float(fr["motion_blur_score"]) for fr in frames]
+    tr, ev = split_indices([fr["file_path"] for fr in frames], eval_mode, eval_interval, scores)
     is_eval_set.update(ev)
     for i, fr in enumerate(frames):
         c2w = torch.tensor(fr["transform_matrix"], dtype=torch.float32)
@@ -435,6 +456,126 @@ def load_seed_points_ply(path: str) -> Tuple[torch.Tensor, torch.Tensor]:
     xyz = data[:, [col["x"], col["y"], col["z"]]]
     rgb = data[:, [col["red"], col["green"], col["blue"]]] / 255.0 if "red" in col else torch.full((n, 3), 0.5)
     return xyz, rgb
+
+
+def velocities_from_poses(c2ws, times=None, loop: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Finite-difference camera-frame velocities of a pose sequence, for datasets that carry poses only: the rule of
+    /root/reference/render_video.py:85-115.  c2ws [F,3 or 4,4] camera-to-world; -> (linear [F,3], angular [F,3]) float64,
+    each in the axes of its own frame's camera (the axes c2ws uses, so OpenGL poses give what transforms.json stores).
+    Frame i is differenced between its neighbours i - 1 and i + 1 — clamped to the ends of an open path, so the ends are
+    one-sided, and taken modulo F when loop is set: world-frame translation difference and the rotation vector (SO(3)
+    log) of R_next R_prev^T, both divided by delta_t and rotated into frame i.  delta_t = times[next] - times[prev];
+    times=None counts in frame indices, delta_t = next - prev as the reference has it (across the wrap of a looped path
+    that is 2 - F, not 2: the reference's own convention, kept).  A single frame has zero velocity."""
+    c2ws = torch.as_tensor(c2ws, dtype=torch.float64)
+    if c2ws.dim() != 3 or c2ws.shape[1] not in (3, 4) or c2ws.shape[2] != 4:
+        raise ValueError(f"c2ws must be [F,3,4] or [F,4,4], got {tuple(c2ws.shape)}")
+    F = int(c2ws.shape[0])
+    idx = torch.arange(F)
+    prev, nxt = ((idx - 1) % F, (idx + 1) % F) if loop else ((idx - 1).clamp(min=0), (idx + 1).clamp(max=F - 1))
+    t = idx.to(torch.float64) if times is None else torch.as_tensor(times, dtype=torch.float64).reshape(F)
+    dt = t[nxt] - t[prev]
+    if F > 1 and bool((dt == 0).any()):
+        raise ValueError("two neighbouring frames share a time stamp")
+    dt = torch.where(dt == 0, torch.ones_like(dt), dt)                  # F == 1: both differences are zero anyway
+    R, p = c2ws[:, :3, :3], c2ws[:, :3, 3]
+    lin_w = (p[nxt] - p[prev]) / dt[:, None]
+    ang_w = _so3_log(R[nxt] @ R[prev].transpose(1, 2)) / dt[:, None]
+    R_wc = R.transpose(1, 2)
+    return (R_wc @ lin_w[:, :, None])[:, :, 0], (R_wc @ ang_w[:, :, None])[:, :, 0]
+
+
+def _so3_log(R: torch.Tensor) -> torch.Tensor:
+    """rotation vectors [...,3] of rotation matrices [...,3,3] (float64), angle in [0, pi]: the angle from atan2 of the
+    antisymmetric part's norm and the trace, the axis from the antisymmetric part — or, within 1e-6 of pi where that
+    vanishes, from the largest column of R + I"""
+    a = torch.stack([R[..., 2, 1] - R[..., 1, 2], R[..., 0, 2] - R[..., 2, 0], R[..., 1, 0] - R[..., 0, 1]], dim=-1)
+    s = a.norm(dim=-1)                                                   # 2 sin(angle)
+    c = R[..., 0, 0] + R[..., 1, 1] + R[..., 2, 2] - 1.0                 # 2 cos(angle)
+    angle = torch.atan2(s, c)
+    small = s < 1e-12
+    scale = torch.where(small, torch.full_like(s, 0.5), angle / torch.where(small, torch.ones_like(s), s))
+    out = a * scale[..., None]
+    flipped = (s < 2e-6) & (c < 0)                                       # angle ~ pi: a carries no direction
+    if bool(flipped.any()):
+        S = R + torch.eye(3, dtype=R.dtype, device=R.device)             # = 2 n n^T at angle pi
+        k = torch.diagonal(S, dim1=-2, dim2=-1).argmax(dim=-1)
+        n = torch.gather(S, -1, k[..., None, None].expand(S.shape[:-1] + (1,)))[..., 0]
+        n = n / n.norm(dim=-1, keepdim=True)
+        sign = torch.where((n * a).sum(-1) < 0, -1.0, 1.0)
+        out = torch.where(flipped[..., None], n * (sign * angle)[..., None], out)
+    return out
+
+
+def camera_arrays(cameras) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """what blur_stats takes, from the cameras' poses and metadata alone: (viewmats [F,4,4], lin [F,3], ang [F,3], intrins
+    [F,4], times [F,2]) float32 on the CPU, poses and velocities through blurscore.view_and_twist"""
+    from .blurscore import view_and_twist
+    c2w = torch.stack([c.camera_to_world[:3].to(dtype=torch.float32, device="cpu") for c in cameras])
+    vel = [torch.tensor([[float(v) for v in c.metadata.get(k, (0.0, 0.0, 0.0))] for c in cameras], dtype=torch.float32)
+           for k in ("camera_linear_velocity", "camera_angular_velocity")]
+    viewmats, lin, ang = view_and_twist(c2w, vel[0], vel[1])
+    intrins = torch.tensor([[c.fx, c.fy, c.cx, c.cy] for c in cameras], dtype=torch.float32)
+    times = torch.tensor([[float(c.metadata.get("exposure_time", 0.0)), float(c.metadata.get("rolling_shutter_time", 0.0))]
+                          for c in cameras], dtype=torch.float32)
+    return viewmats, lin, ang, intrins, times
+
+
+def blur_stats(scene: "TransformsScene", points: torch.Tensor):
+    """blurscore.BlurStats of every frame of `scene` (in its camera order) over `points` [N,3] — the seed cloud, say — from
+    the dataset's own poses, velocities and times, no model: on points' device (a GPU cloud takes the HIP kernels)."""
+    from .blurscore import blur_stats as _stats
+    cams = scene.cameras
+    if not cams:
+        raise ValueError("the scene has no frames")
+    if any((c.width, c.height) != (cams[0].width, cams[0].height) for c in cams):
+        raise ValueError("blur_stats needs frames of one size")
+    points = points.detach().to(torch.float32)
+    arrays = (t.to(points.device) for t in camera_arrays(cams))
+    return _stats(points, *arrays, cams[0].width, cams[0].height)
+
+
+def blur_scores(scene: "TransformsScene", points: torch.Tensor) -> List[float]:
+    """one motion_blur_score per frame of `scene`: the mean streak length in pixels (blur_stats(...).mean_blur)"""
+    return [float(v) for v in blur_stats(scene, points).mean_blur.tolist()]
+
+
+def write_blur_scored(src_root: str, dst_root: str, scores=None, interval: int = 8) -> str:
+    """Write the blur-scored copy of the dataset at src_root to dst_root, as
+    /root/reference/train_eval_split_by_blur_score.py:6-57 does: frames sorted by file_path and cut into runs of `interval`,
+    the frame with the smallest score of each run copied to images/eval_<name>, the others to images/train_<name>,
+    file_path rewritten to the copy, every other key of transforms.json kept, sparse_pc.ply copied when there is one.
+    scores: one per frame in path-sorted order (the order of load_transforms' cameras), stored as motion_blur_score; None
+    uses the scores the file holds (ValueError when a frame has none).  An image is looked up at src_root/<file_path>.
+    load_transforms(dst_root, eval_mode="filename") then reads the split.  -> the path of the written transforms.json"""
+    import shutil
+    if os.path.abspath(src_root) == os.path.abspath(dst_root):
+        raise ValueError("write_blur_scored writes a copy: dst_root must differ from src_root")
+    with open(os.path.join(src_root, "transforms.json"), "rt") as f:
+        meta = json.load(f)
+    frames = meta["frames"] = sorted(meta["frames"], key=lambda fr: fr["file_path"])
+    if scores is not None:
+        if len(scores) != len(frames):
+            raise ValueError(f"{len(scores)} scores for {len(frames)} frames")
+        for fr, sc in zip(frames, scores):
+            fr["motion_blur_score"] = float(sc)
+    paths = [fr["file_path"] for fr in frames]
+    if any("motion_blur_score" not in fr for fr in frames):
+        raise ValueError("a frame carries no motion_blur_score and no scores were given")
+    _, ev = split_indices(paths, "blur_score", interval, [fr["motion_blur_score"] for fr in frames])
+    os.makedirs(os.path.join(dst_root, "images"), exist_ok=True)
+    chosen = set(ev)
+    for i, fr in enumerate(frames):
+        name = ("eval_" if i in chosen else "train_") + os.path.basename(paths[i])
+        shutil.copyfile(os.path.join(src_root, paths[i]), os.path.join(dst_root, "images", name))
+        fr["file_path"] = os.path.join("images", name)
+    ply = os.path.join(src_root, "sparse_pc.ply")
+    if os.path.exists(ply):
+        shutil.copyfile(ply, os.path.join(dst_root, "sparse_pc.ply"))
+    out = os.path.join(dst_root, "transforms.json")
+    with open(out, "wt") as f:
+        json.dump(meta, f, indent=4)
+    return out
 
 
 def synthetic_scene(n: int, width: int, height: int, sh_degree: int = 3, seed: int = 1234,

@@ -16,7 +16,7 @@ The forward/backward rendering surface; the densification step that follows it l
 from __future__ import annotations
 
 from dataclasses import dataclass, field
-from typing import Dict, Optional, Tuple
+from typing import Dict, List, Optional, Tuple
 
 import torch
 from torch import Tensor, nn
@@ -713,6 +713,32 @@ class SplatfactoDeblurModel(nn.Module):
             return self.get_outputs(camera)             # eval mode: never colour-corrected
         finally:
             self.train(was)
+
+    @torch.no_grad()
+    def blur_stats(self, cameras, points: Optional[Tensor] = None):
+        """blurscore.BlurStats of `cameras` (one entry per camera, in their order) over `points` [N,3] (default: the
+        model's means): how many pixels each frame is smeared and sheared by, as THIS model renders it — every camera's
+        effective pose and twist from _viewmat_and_velocity (pose and velocity adjustments included, data velocities
+        dropped under zero_initial_velocities) and its effective exposure and readout from shutter_times (the learned
+        ones included).  All cameras must share one image size.  On the model's device; no gradient."""
+        from .blurscore import blur_stats
+        cameras = list(cameras)
+        if not cameras:
+            raise ValueError("blur_stats needs at least one camera")
+        W, H = cameras[0].width, cameras[0].height
+        if any((c.width, c.height) != (W, H) for c in cameras):
+            raise ValueError("blur_stats needs cameras of one image size")
+        dev = self.means.device
+        views = [self._viewmat_and_velocity(c) for c in cameras]
+        times = [torch.stack(self.shutter_times(c)) for c in cameras]
+        intrins = torch.tensor([[c.fx, c.fy, c.cx, c.cy] for c in cameras], dtype=torch.float32).to(dev)
+        pts = self.means if points is None else points.to(device=dev, dtype=torch.float32)
+        return blur_stats(pts.detach(), *(torch.stack([v[k] for v in views]).detach().float() for k in range(3)), intrins,
+                          torch.stack(times).detach().float(), W, H)
+
+    def blur_scores(self, cameras) -> List[float]:
+        """one motion_blur_score per camera: blur_stats(cameras).mean_blur, the mean streak length in pixels"""
+        return [float(v) for v in self.blur_stats(cameras).mean_blur.tolist()]
 
     @staticmethod
     def from_scene(config: SplatfactoDeblurConfig, scene: Dict, device, num_cameras: int = 1):

@@ -831,6 +831,28 @@ long long gs_knn_workspace_bytes(int N, int k);
 int gs_knn(int N, const float* xyz, int k, float cell_size, int max_rings, float* dists, int* idx, int* stats, void* ws,
            long long ws_bytes, void* stream);
 
+/* ---- per-frame blur statistics of a point cloud under the motion model (csrc/blur_math.h states every formula;
+ * blurscore.py drives it): how many pixels the camera's twist smears a frame by during its exposure, and how far its
+ * rolling shutter shears it.  No allocation, no state, no atomics; two runs agree bit for bit.
+ *
+ * points [N,3] fp32; per frame f: viewmats [F,16] row-major world-to-camera (OpenCV axes), lin / ang [F,3] the camera's
+ * body twist in that frame, intrins [F,4] = fx fy cx cy, times [F,2] = exposure E, readout T.  For every pair, in fp32
+ * without fused multiply-add: pc = V p, (u, v) its pixel, pv its pixel velocity (the renderer's pixel_velocity),
+ * blur = E |pv|, skew = T |pv| |v / H - 1/2|.  A pair is visible iff pc.z > clip and 0 <= u < W and 0 <= v < H.  Over
+ * the visible pairs of frame f: counts[f] their number, stats[f*4 ..] = mean blur, rms blur, max blur, mean skew (sums in
+ * float64, in an order fixed by N); all zero when no pair is visible.  F == 0 or N == 0 launch nothing (N == 0 clears
+ * counts and stats).  F <= 65535 * 32, N <= 2^30, W, H >= 1; anything else is GS_ERR_INVALID before any launch.
+ * ws: 8-byte aligned, gs_blur_stats_workspace_bytes(F, N) bytes (-1 on invalid arguments; 32 bytes per frame and 1024
+ * points).  gs_blur_stats_ppt is the same call with the points a thread keeps in registers chosen by the caller (1, 2, 4,
+ * 8, 16; <= 0: the default) — a tuning knob that reorders the float64 sums and nothing else. */
+long long gs_blur_stats_workspace_bytes(int F, int N);
+int gs_blur_stats(int F, int N, const float* points, const float* viewmats, const float* lin, const float* ang,
+                  const float* intrins, const float* times, int W, int H, float clip, int* counts, float* stats,
+                  void* ws, long long ws_bytes, void* stream);
+int gs_blur_stats_ppt(int F, int N, const float* points, const float* viewmats, const float* lin, const float* ang,
+                      const float* intrins, const float* times, int W, int H, float clip, int points_per_thread,
+                      int* counts, float* stats, void* ws, long long ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
