@@ -33,6 +33,8 @@ SOURCES = [
     ("knn.hip", ["-ffp-contract=off"]),
     # per-frame blur statistics (blurscore.py): per-pair values round every operation, as the host build's do
     ("blur.hip", ["-ffp-contract=off"]),
+    # depth-prior loss (depthprior.py): per-pixel values round every operation, as the host build's do
+    ("depthprior.hip", ["-ffp-contract=off"]),
     ("frame.hip", []),           # host-side frame orchestration (no kernels of its own)
 ]
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-fvisibility=hidden"]

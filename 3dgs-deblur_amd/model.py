@@ -493,7 +493,7 @@ class SplatfactoDeblurModel(nn.Module):
             out["depth"] = None
         return out
 
-    def render_and_backward(self, camera: Camera, grad_image, grad_depth=None) -> Tensor:
+    def render_and_backward(self, camera: Camera, grad_image, grad_depth=None, grad_depth_sums=None) -> Tensor:
         """One TRAINING frame, forward and backward in one host call (step.render_step: the same C-ABI calls as
         get_outputs + Tensor.backward, without the autograd engine between the two compositors — the entry bench.py
         times).  grad_image: callable rgb [H,W,3] -> d loss / d rgb, where rgb is what get_outputs()["rgb"] would hold
@@ -503,8 +503,13 @@ class SplatfactoDeblurModel(nn.Module):
         grad_depth (optional): callable (depth [H,W,1], accumulation [H,W,1]) -> d loss / d depth [H,W,1], where depth is
         what get_outputs()["depth"] would hold (expected_depth); its chain to the per-sample depth sums and alphas runs
         here, and the frame's backward takes the depth term (step.render_step grad_depth).  None: rgb and every gradient
-        exactly as without it."""
+        exactly as without it.
+        grad_depth_sums (optional, instead of grad_depth: both is a ValueError): callable (depth_acc [S,H,W], alphas
+        [S,H,W]) -> (d loss / d depth_acc, d loss / d alphas), handed to step.render_step(grad_depth=) as it is — a loss
+        that starts from the compositor's raw sums (depthprior.depth_prior_loss_with_grad) builds no expected_depth graph."""
         from .step import render_step
+        if grad_depth is not None and grad_depth_sums is not None:
+            raise ValueError("render_and_backward takes grad_depth or grad_depth_sums, not both")
         cfg = self.config
         dev = self.means.device
         d = self.downscale_factor()
@@ -532,7 +537,7 @@ class SplatfactoDeblurModel(nn.Module):
             v = grad_image(torch.clamp(rgb, max=1.0))
             return v * (rgb <= 1.0)
 
-        v_depth = None
+        v_depth = grad_depth_sums
         if grad_depth is not None:
             def v_depth(depth_acc, alphas):
                 da, al = depth_acc.requires_grad_(True), alphas.requires_grad_(True)

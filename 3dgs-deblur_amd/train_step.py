@@ -95,6 +95,28 @@ def depth_loss(depth: Tensor, gt_depth: Tensor, depth_lambda: float) -> Tensor:
     return depth_lambda * (torch.abs(depth - gt_depth) * valid).sum() / n
 
 
+_metric_depth_loss = depth_loss          # train_step's depth_loss= keyword shadows the function inside it
+DEPTH_LOSSES = (None, "l1", "pearson")
+DEPTH_SPACES = ("depth", "disparity")
+
+
+def _check_depth_prior(depth_loss, depth_space) -> None:
+    """train_step's depth_loss= / depth_space= names, checked before anything is launched"""
+    if depth_loss not in DEPTH_LOSSES:
+        raise ValueError(f"unknown depth_loss {depth_loss!r} (one of {DEPTH_LOSSES})")
+    if depth_space not in DEPTH_SPACES:
+        raise ValueError(f"unknown depth_space {depth_space!r} (one of {DEPTH_SPACES})")
+
+
+def depth_prior_term(depth: Tensor, accumulation: Tensor, prior: Tensor, kind: str, space: str, weight: float) -> Tensor:
+    """depthprior.depth_prior_loss of a rendered depth map (autograd and batch routes): depth, accumulation, prior
+    [H,W,1]; depth_acc = depth * m, alphas = m with m = (accumulation > 0), one sample, so that x is the depth itself"""
+    from .depthprior import depth_prior_loss
+    H, W = int(depth.shape[0]), int(depth.shape[1])
+    m = (accumulation > 0).to(depth.dtype).reshape(1, H, W)
+    return depth_prior_loss(depth.reshape(1, H, W) * m, m, prior.reshape(H, W), kind, space, weight)
+
+
 def scale_regularization(log_scales: Tensor, max_gauss_ratio: float = 10.0) -> Tensor:
     """Penalise needle-like Gaussians (PhysGaussian-style, as in splatfacto): mean(max(s_max/s_min, r) - r)."""
     s = torch.exp(log_scales)
@@ -312,15 +334,24 @@ def one_call_route(model: SplatfactoDeblurModel) -> bool:
 
 def train_step(model: SplatfactoDeblurModel, optimizers: Dict[str, torch.optim.Optimizer], camera: Camera,
                gt_image: Tensor, ssim_lambda: float = 0.2, allreduce: Optional[str] = None,
-               gt_depth: Optional[Tensor] = None, depth_lambda: float = 0.0) -> Dict[str, float]:
+               gt_depth: Optional[Tensor] = None, depth_lambda: float = 0.0, depth_loss: Optional[str] = None,
+               depth_space: str = "depth") -> Dict[str, float]:
     """One training iteration: render (HIP) -> loss -> backward (HIP) -> [DP gradient all-reduce] -> Adam.
     camera / gt_image (/ gt_depth) may be lists: B cameras rendered as one batch (model.get_outputs_batch), the loss
     the mean over the cameras of the per-image loss, on the autograd route.
     gt_depth [H,W,1] (scene units, 0 = no measurement) with depth_lambda > 0 adds depth_loss(out["depth"], gt_depth)
-    to the loss, on either route (the depth map follows the resolution schedule: downscale_depth)."""
+    to the loss, on either route (the depth map follows the resolution schedule: downscale_depth).
+    depth_loss "pearson" / "l1" (None: the metric L1 above, unchanged): gt_depth is a depth PRIOR and the term is
+    depthprior.depth_prior_loss(kind=depth_loss, space=depth_space, weight=depth_lambda) — "pearson" for a monocular prior
+    known up to scale and shift, depth_space="disparity" for one given as inverse depth.  On the one-call route the op
+    takes the compositor's per-sample sums between the two halves (render_and_backward grad_depth_sums: no torch op for
+    the depth term), on the autograd and batch routes the rendered depth map (depth_prior_term).  Unknown names raise
+    ValueError before anything is launched."""
+    _check_depth_prior(depth_loss, depth_space)
     if isinstance(camera, (list, tuple)):
         return _train_step_batch(model, optimizers, list(camera), list(gt_image), ssim_lambda, allreduce,
-                                 gt_depth, depth_lambda)
+                                 gt_depth, depth_lambda, depth_loss, depth_space)
+    depth_kind, depth_loss = depth_loss, _metric_depth_loss      # below, depth_loss is the module's function again
     model.train()
     for o in optimizers.values():
         o.zero_grad(set_to_none=True)
@@ -354,7 +385,18 @@ def train_step(model: SplatfactoDeblurModel, optimizers: Dict[str, torch.optim.O
                 depth = depth.requires_grad_(True)
                 box["depth_loss"] = dl = depth_loss(depth, gt_depth, depth_lambda)
                 return torch.autograd.grad(dl, depth)[0]
-        rgb = model.render_and_backward(camera, grad_image, grad_depth)
+        if use_depth and depth_kind is not None:
+            # the prior loss starts from the compositor's raw sums: one kernel pair between the two halves, no torch op
+            from .depthprior import depth_prior_loss_with_grad
+            prior = gt_depth.reshape(gt_depth.shape[0], gt_depth.shape[1])
+
+            def grad_depth_sums(depth_acc, alphas):
+                box["depth_loss"], v_acc, v_al = depth_prior_loss_with_grad(depth_acc, alphas, prior, depth_kind,
+                                                                            depth_space, depth_lambda)
+                return v_acc, v_al
+            rgb = model.render_and_backward(camera, grad_image, grad_depth_sums=grad_depth_sums)
+        else:
+            rgb = model.render_and_backward(camera, grad_image, grad_depth)
         rgb = box.get("rgb", rgb)                          # the logged PSNR is of the corrected image
         loss = box["loss"]
         if use_depth:
@@ -378,7 +420,10 @@ def train_step(model: SplatfactoDeblurModel, optimizers: Dict[str, torch.optim.O
         out = model.get_outputs(camera, return_depth=True) if use_depth else model.get_outputs(camera)
         rgb = out["rgb"].detach()
         loss = image_loss(out["rgb"], gt_image, ssim_lambda)
-        if use_depth:
+        if use_depth and depth_kind is not None:
+            loss = loss + depth_prior_term(out["depth"], out["accumulation"], gt_depth, depth_kind, depth_space,
+                                           depth_lambda)
+        elif use_depth:
             loss = loss + depth_loss(out["depth"], gt_depth, depth_lambda)
         if model.config.use_scale_regularization:
             loss = loss + scale_regularization(model.scales)
@@ -412,9 +457,13 @@ def _dp_allreduce(model: SplatfactoDeblurModel, allreduce: str) -> None:
 
 
 def _train_step_batch(model: SplatfactoDeblurModel, optimizers, cameras, gt_images, ssim_lambda, allreduce,
-                      gt_depths, depth_lambda) -> Dict[str, float]:
+                      gt_depths, depth_lambda, depth_loss: Optional[str] = None,
+                      depth_space: str = "depth") -> Dict[str, float]:
     """train_step for B cameras: one get_outputs_batch, loss = mean over the cameras of train_step's per-image loss
-    (image loss + optional depth loss), one autograd backward, one optimizer step"""
+    (image loss + optional depth loss; depth_loss / depth_space as train_step's), one autograd backward, one optimizer
+    step"""
+    _check_depth_prior(depth_loss, depth_space)
+    depth_kind, depth_loss = depth_loss, _metric_depth_loss      # below, depth_loss is the module's function again
     if len(cameras) != len(gt_images) or not cameras:
         raise ValueError("train_step needs as many images as cameras")
     model.train()
@@ -429,7 +478,10 @@ def _train_step_batch(model: SplatfactoDeblurModel, optimizers, cameras, gt_imag
     losses = []
     for b in range(len(cameras)):
         l_b = image_loss(out["rgb"][b], gts[b], ssim_lambda)
-        if use_depth and gt_depths[b] is not None:
+        if use_depth and gt_depths[b] is not None and depth_kind is not None:
+            l_b = l_b + depth_prior_term(out["depth"][b], out["accumulation"][b], gt_depths[b], depth_kind, depth_space,
+                                         depth_lambda)
+        elif use_depth and gt_depths[b] is not None:
             l_b = l_b + depth_loss(out["depth"][b], gt_depths[b], depth_lambda)
         losses.append(l_b)
     loss = torch.stack([l.reshape(()) for l in losses]).mean()
@@ -522,12 +574,13 @@ def train_scene(model: SplatfactoDeblurModel, scene, images, iterations: int, lr
                 ssim_lambda: float = 0.2, optimize_eval_cameras: bool = False, eval_camera_every: int = 4,
                 densify=None, log_every: int = 0, seed: int = 0, depths=None, depth_lambda: float = 0.0,
                 batch_size: int = 1, optimizer: Optional[str] = None, checkpoint_path=None, checkpoint_every: int = 0,
-                resume=None) -> Dict:
+                resume=None, depth_loss: Optional[str] = None, depth_space: str = "depth") -> Dict:
     """Train on scene.train_indices (one view per step, seeded shuffle), optionally refining the evaluation cameras
     in between; returns {'results': {psnr, ssim}, 'wall_clock_time_seconds', 'history'} like the reference's
     metrics.json (/root/reference/train.py:87-100, parse_outputs.py:58); with config.color_corrected_metrics the results
     also carry cc_psnr / cc_ssim (evaluate).  depths (optional): per-frame depth maps
     [H,W,1] or None, indexed like images (data.load_depth); with depth_lambda > 0 every step adds the depth loss.
+    depth_loss / depth_space: train_step's — "pearson" (or "l1") takes the maps as depth PRIORS (depthprior).
     batch_size > 1: every step takes that many views of the shuffle (fewer at the end of a pass) as one batch
     (train_step with lists), and the evaluation renders in batches of that size.  optimizer: make_optimizers' choice
     ("adam" / "selective_adam"; default model.config.optimizer).  densify: a densify.DensifyConfig (splatfacto's split /
@@ -542,6 +595,7 @@ def train_scene(model: SplatfactoDeblurModel, scene, images, iterations: int, lr
     import time
     from . import mcmc as M
     use_mcmc = isinstance(densify, M.MCMCConfig)
+    _check_depth_prior(depth_loss, depth_space)
     if checkpoint_every and checkpoint_path is None:
         raise ValueError("checkpoint_every needs checkpoint_path")
     loaded = None
@@ -605,12 +659,12 @@ def train_scene(model: SplatfactoDeblurModel, scene, images, iterations: int, lr
             ids = [order.pop() for _ in range(min(batch_size, len(order)))]
             gd = [depths[i] for i in ids] if depths is not None else None
             h = train_step(model, optimizers, [scene.cameras[i] for i in ids], [images[i] for i in ids], ssim_lambda,
-                           gt_depth=gd, depth_lambda=depth_lambda)
+                           gt_depth=gd, depth_lambda=depth_lambda, depth_loss=depth_loss, depth_space=depth_space)
         else:
             i = order.pop()
             gd = depths[i] if depths is not None else None
             h = train_step(model, optimizers, scene.cameras[i], images[i], ssim_lambda, gt_depth=gd,
-                           depth_lambda=depth_lambda)
+                           depth_lambda=depth_lambda, depth_loss=depth_loss, depth_space=depth_space)
         if use_mcmc:
             M.step_callback(model, optimizers, it, densify)
         elif densify is not None:

@@ -853,6 +853,29 @@ int gs_blur_stats_ppt(int F, int N, const float* points, const float* viewmats, 
                       const float* intrins, const float* times, int W, int H, float clip, int points_per_thread,
                       int* counts, float* stats, void* ws, long long ws_bytes, void* stream);
 
+/* ---- scale- and shift-invariant depth-prior loss (csrc/depthprior_math.h states every formula; depthprior.py drives
+ * it): a monocular depth prior, known up to scale and shift, against the rendered depth.  No allocation, no state, no
+ * atomics, two launches, nothing read back; two runs agree bit for bit and a frame's results do not depend on the rest
+ * of the batch.
+ *
+ * depth_acc, alphas [B,S,H,W] fp32: the compositor's per-sample sums (weight * camera-space depth; 1 - transmittance).
+ * prior [B,H,W] fp32, 0 (or less): no value.  Per pixel, in fp32 without fused multiply-add: d = the samples of depth_acc
+ * added in order, divided by S; a likewise; valid iff prior > 0 and a > min_alpha (and d > 0 with space 1); x = d / a
+ * (space 0, depth) or a / d (space 1, disparity); y = prior.  Over the valid pixels of frame b, in float64 in an order
+ * fixed by H * W: n, sum x, sum y, sum xx, sum yy, sum xy (and sum |x - y| for kind 1).
+ * kind 0 (pearson): loss_out[b] = weight * (1 - rho), rho = (n sxy - sx sy) / sqrt((n sxx - sx^2)(n syy - sy^2)); with
+ * n < 2, or either variance term not above 1e-12 * n * sxx (syy), the loss and every gradient are exactly 0.
+ * kind 1 (l1): loss_out[b] = weight * sum |x - y| / max(n, 1).
+ * v_depth_acc, v_alphas [B,S,H,W] receive d loss_out[b] / d depth_acc, d alphas (float64 chain, rounded once; the same
+ * value for every sample of a pixel; exact zeros at invalid pixels).  stats_out [B*8] float64: the seven sums, then rho
+ * (0 for kind 1 or a degenerate frame).  1 <= S, B * S <= 256, H, W >= 1, B * S * H * W < 2^30, min_alpha >= 0, kind and
+ * space 0 or 1; anything else is GS_ERR_INVALID before any launch.  B == 0 launches nothing.  ws: 8-byte aligned,
+ * gs_depth_prior_workspace_bytes(B, S, H, W) bytes (-1 on invalid arguments; 56 bytes per frame and 4096 pixels). */
+long long gs_depth_prior_workspace_bytes(int B, int S, int H, int W);
+int gs_depth_prior_loss(int B, int S, int H, int W, const float* depth_acc, const float* alphas, const float* prior,
+                        int kind, int space, float min_alpha, float weight, float* loss_out, double* stats_out,
+                        float* v_depth_acc, float* v_alphas, void* ws, long long ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

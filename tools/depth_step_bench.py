@@ -1,10 +1,13 @@
 """What a depth loss costs per training step: the headline scene (bench.py's 1M Gaussians, 1920x1080, S = 5 sub-poses)
-through render_step with the rgb gradient only, and with the rgb gradient plus an L1 loss on the expected depth (the chain
-SplatfactoDeblurModel.render_and_backward runs: d loss / d depth -> d loss / d depth_acc, d loss / d alphas).  The two
-forms are alternated in blocks within one process, so both see the same clocks; the line printed is JSON.
+through render_step with the rgb gradient only (rgb), with the rgb gradient plus an L1 loss on the expected depth as a
+chain of torch ops (depth: the chain SplatfactoDeblurModel.render_and_backward runs: d loss / d depth -> d loss /
+d depth_acc, d loss / d alphas), and with the depth-prior kernels on the raw sums in its place (fused_l1, fused_pearson:
+depthprior.depth_prior_loss_with_grad, what train_step's depth_loss="l1" / "pearson" runs).  The forms are alternated in
+blocks within one process, so all see the same clocks; the line printed is JSON and is appended to --out.
 
-    python tools/depth_step_bench.py [--steps 30] [--blocks 4] [--warmup 5]
-    python tools/depth_step_bench.py --mode depth --steps 20   # one form only (for a rocprofv3 --kernel-trace --stats run)
+    python tools/depth_step_bench.py [--steps 30] [--blocks 4] [--warmup 5]              # rgb and depth
+    python tools/depth_step_bench.py --mode all                                          # the four forms
+    python tools/depth_step_bench.py --mode fused_pearson --steps 20   # one form only (for a rocprofv3 --kernel-trace --stats run)
 """
 from __future__ import annotations
 
@@ -24,7 +27,9 @@ def main() -> None:
     ap.add_argument("--steps", type=int, default=30, help="timed steps per block")
     ap.add_argument("--blocks", type=int, default=4, help="blocks per form, alternated")
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--mode", choices=("both", "rgb", "depth"), default="both")
+    ap.add_argument("--mode", choices=("both", "all", "rgb", "depth", "fused_l1", "fused_pearson"), default="both")
+    ap.add_argument("--out", default=str(ROOT / "profiles" / "depth_prior_bench.jsonl"),
+                    help="--mode all appends its line here ('' to only print)")
     args = ap.parse_args()
 
     import torch
@@ -52,20 +57,29 @@ def main() -> None:
         loss = 0.1 * ((depth - gt).abs() * (gt > 0)).sum() / n_valid
         return torch.autograd.grad(loss, (da, a), allow_unused=True)
 
-    def step(depth: bool):
+    prior = gt.reshape(H, W).contiguous()
+
+    def fused(kind):
+        def grad_depth_sums(depth_acc, al):
+            return gs.depth_prior_loss_with_grad(depth_acc, al, prior, kind, "depth", 0.1)[1:]
+        return grad_depth_sums
+
+    callables = {"rgb": None, "depth": grad_depth, "fused_l1": fused("l1"), "fused_pearson": fused("pearson")}
+
+    def step(form: str):
         gs.render_step(p["means"], p["log_scales"], p["quats"], p["opacity_logits"], p["sh"], wl.viewmat, wl.lin, wl.ang,
                        wl.times_t, wl.bg, S, 1, sc["fx"], sc["fy"], sc["cx"], sc["cy"], H, W, wl.wt, gamma=2.2,
-                       min_rgb_level=10.0, raw_params=True, hints=wl.hints, grad_depth=grad_depth if depth else None)
+                       min_rgb_level=10.0, raw_params=True, hints=wl.hints, grad_depth=callables[form])
 
-    def block(depth: bool, n: int) -> float:
+    def block(form: str, n: int) -> float:
         torch.cuda.synchronize()
         t = time.perf_counter()
         for _ in range(n):
-            step(depth)
+            step(form)
         torch.cuda.synchronize()
         return (time.perf_counter() - t) * 1e3 / n
 
-    forms = {"both": (False, True), "rgb": (False,), "depth": (True,)}[args.mode]
+    forms = {"both": ("rgb", "depth"), "all": ("rgb", "depth", "fused_l1", "fused_pearson")}.get(args.mode, (args.mode,))
     for f in forms:
         block(f, args.warmup)
     ms = {f: [] for f in forms}
@@ -74,13 +88,19 @@ def main() -> None:
             ms[f].append(block(f, args.steps))
     res = {"scene": "1M Gaussians, 1920x1080, S=5 (bench.py headline)", "steps_per_block": args.steps,
            "blocks": args.blocks}
+    keys = {"rgb": "rgb_only", "depth": "rgb_depth", "fused_l1": "rgb_fused_l1", "fused_pearson": "rgb_fused_pearson"}
     for f in forms:
-        key = "rgb_depth" if f else "rgb_only"
-        res[key + "_ms_per_step"] = round(statistics.median(ms[f]), 4)
-        res[key + "_blocks_ms"] = [round(x, 4) for x in ms[f]]
-    if len(forms) == 2:
+        res[keys[f] + "_ms_per_step"] = round(statistics.median(ms[f]), 4)
+        res[keys[f] + "_blocks_ms"] = [round(x, 4) for x in ms[f]]
+    if args.mode == "both":
         res["ratio"] = round(res["rgb_depth_ms_per_step"] / res["rgb_only_ms_per_step"], 4)
+    if args.mode == "all":
+        for f in ("depth", "fused_l1", "fused_pearson"):
+            res[keys[f] + "_extra_ms"] = round(res[keys[f] + "_ms_per_step"] - res["rgb_only_ms_per_step"], 4)
     print(json.dumps(res))
+    if args.mode == "all" and args.out:
+        with open(args.out, "at") as f:
+            f.write(json.dumps({"tool": "depth_step_bench", **res}) + "\n")
 
 
 if __name__ == "__main__":

@@ -11,7 +11,8 @@ Variants follow /root/reference/train.py:29-76: blur_samples 0 = no motion-blur 
 touching the Gaussians (train.py:180-183); --densify adds splatfacto's refinement schedule or 3DGS-MCMC (--cap-max);
 --bilateral-grid learns a per-image colour correction with the scene; --color-corrected-metrics adds cc_psnr / cc_ssim
 (the evaluation renders fitted to their images by a quadratic colour warp first); --optimize-exposure / --optimize-readout learn the
-exposure and rolling-shutter readout times from their metadata values.  Every variant leaves checkpoint_<name>.pt beside
+exposure and rolling-shutter readout times from their metadata values; --depth-lambda adds a depth term on the dataset's
+depth maps (--depth-loss pearson: monocular priors known up to scale and shift).  Every variant leaves checkpoint_<name>.pt beside
 its metrics_<name>.json (--checkpoint-every K: also every K steps; --resume PATH continues from one; --export-ply adds
 splat_<name>.ply for a viewer); tools/render_model.py renders either file."""
 import argparse
@@ -28,7 +29,7 @@ sys.path.insert(0, str(Path(__file__).resolve().parent))
 import synthetic_dataset as SD  # noqa: E402  (test / demo data generation: not part of the product package)
 
 
-def main():
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--data", default=None)
     ap.add_argument("--generate", default=None, help="write the synthetic dataset here first (and use it)")
@@ -74,7 +75,22 @@ def main():
                     help="start from N random Gaussians (splatfacto's random_init) instead of the dataset's seed cloud: "
                          "for scenes without one")
     ap.add_argument("--random-scale", type=float, default=10.0, help="--random-init: side of the cube the means are drawn in")
+    ap.add_argument("--depth-lambda", type=float, default=0.0,
+                    help="weight of the depth term; > 0 loads the maps the dataset's depth_file_path entries name "
+                         "(data.load_scene_depths)")
+    ap.add_argument("--depth-loss", default=None, choices=["l1", "pearson"],
+                    help="pearson: 1 - correlation with a monocular depth PRIOR known only up to scale and shift (for such "
+                         "a relative prior the dataset's depth unit factor is irrelevant); l1: mean |x - prior| over the "
+                         "covered pixels with a value.  Default: the metric L1 of depth supervision (maps in scene units)")
+    ap.add_argument("--depth-space", default="depth", choices=["depth", "disparity"],
+                    help="--depth-loss l1 / pearson: compare the rendered depth, or its inverse (a prior given as inverse "
+                         "depth, as MiDaS and Depth Anything give it)")
     ap.add_argument("--out", default="gpurun_out/deblur")
+    return ap
+
+
+def main():
+    ap = build_parser()
     args = ap.parse_args()
     if args.resume and not os.path.isdir(args.resume) and len(args.blur_samples) != 1:
         ap.error("--resume FILE continues one variant: give one --blur-samples value, or a directory")
@@ -86,6 +102,11 @@ def main():
                     rolling_shutter_time=args.rolling_shutter_time)
     scene = gs.load_transforms(root)
     images = gs.data.load_scene_images(scene, dev)          # undistorts when the scene carries lens coefficients
+    depths = None
+    if args.depth_lambda > 0:
+        depths = gs.data.load_scene_depths(scene, dev)           # follows the images' undistortion and crop; None where absent
+        if all(d is None for d in depths):
+            ap.error("--depth-lambda > 0, but no frame of the dataset names a depth_file_path")
     if args.random_init <= 0:
         if not scene.ply_file_path:
             ap.error("the dataset names no seed cloud (ply_file_path): give --random-init N")
@@ -134,7 +155,9 @@ def main():
         res = gs.training.train_scene(model, scene, images, args.iterations,
                                       optimize_eval_cameras=args.optimize_eval_cameras, log_every=100,
                                       densify=dcfg, checkpoint_path=os.path.join(args.out, f"checkpoint_{name}.pt"),
-                                      checkpoint_every=args.checkpoint_every, resume=resume)
+                                      checkpoint_every=args.checkpoint_every, resume=resume, depths=depths,
+                                      depth_lambda=args.depth_lambda, depth_loss=args.depth_loss,
+                                      depth_space=args.depth_space)
         if args.export_ply:
             gs.checkpoint.export_ply(os.path.join(args.out, f"splat_{name}.ply"), model)
         with open(os.path.join(args.out, f"metrics_{name}.json"), "wt") as f:
