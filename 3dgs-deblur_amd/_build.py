@@ -35,6 +35,8 @@ SOURCES = [
     ("blur.hip", ["-ffp-contract=off"]),
     # depth-prior loss (depthprior.py): per-pixel values round every operation, as the host build's do
     ("depthprior.hip", ["-ffp-contract=off"]),
+    # TSDF fusion and mesh extraction (tsdf.py): the update rounds every operation, as the host build's does
+    ("tsdf.hip", ["-ffp-contract=off"]),
     ("frame.hip", []),           # host-side frame orchestration (no kernels of its own)
 ]
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-fvisibility=hidden"]

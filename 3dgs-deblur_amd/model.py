@@ -15,6 +15,7 @@ The forward/backward rendering surface; the densification step that follows it l
 """
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Tuple
 
@@ -161,6 +162,8 @@ def expected_depth(depth_acc: Tensor, alphas: Tensor) -> Tensor:
 
 class SplatfactoDeblurModel(nn.Module):
     """Gaussian parameters + ``get_outputs`` through the fused HIP path."""
+
+    _sharp = False          # set by sharp_outputs for the length of one render: exposure and readout count as 0
 
     def __init__(self, config: SplatfactoDeblurConfig, means: Tensor, log_scales: Tensor, quats: Tensor,
                  opacity_logits: Tensor, features_dc: Tensor, features_rest: Tensor, num_cameras: int = 1):
@@ -353,7 +356,10 @@ class SplatfactoDeblurModel(nn.Module):
 
     def _base_times(self, camera: Camera) -> Tuple[float, float]:
         """(E0, T0): the camera's metadata exposure / rolling-shutter time; for a quantity the shutter optimizer learns, a
-        metadata value of 0 (or none) is replaced by camera_shutter_optimizer.initial_*, and 0 there too is a ValueError"""
+        metadata value of 0 (or none) is replaced by camera_shutter_optimizer.initial_*, and 0 there too is a ValueError.
+        Inside sharp_outputs both are 0: one sample at the camera's effective pose."""
+        if self._sharp:
+            return 0.0, 0.0
         exposure = float(camera.metadata.get("exposure_time", 0.0))
         readout = float(camera.metadata.get("rolling_shutter_time", 0.0))
         sh = self.config.camera_shutter_optimizer
@@ -397,7 +403,7 @@ class SplatfactoDeblurModel(nn.Module):
     def _rs_time(self, camera: Camera) -> float:
         """readout time handed to the exact rolling-shutter compositors (0: off)"""
         cfg = self.config
-        if cfg.rolling_shutter_mode != "exact" or not cfg.rolling_shutter_compensation:
+        if cfg.rolling_shutter_mode != "exact" or not cfg.rolling_shutter_compensation or self._sharp:
             return 0.0
         return float(camera.metadata.get("rolling_shutter_time", 0.0))
 
@@ -718,6 +724,78 @@ class SplatfactoDeblurModel(nn.Module):
             return self.get_outputs(camera)             # eval mode: never colour-corrected
         finally:
             self.train(was)
+
+    @torch.no_grad()
+    def sharp_outputs(self, camera: Camera) -> Dict[str, Tensor]:
+        """get_outputs_for_camera with exposure and readout 0: one sample at the camera's effective pose (pose adjustment
+        included, cam_idx kept), whatever the metadata and the shutter optimizer hold — the render without motion blur."""
+        was = self.training
+        self.eval()
+        self._sharp = True
+        try:
+            return self.get_outputs(camera)
+        finally:
+            self._sharp = False
+            self.train(was)
+
+    @torch.no_grad()
+    def fuse_tsdf(self, cameras, volume=None, resolution: int = 256, bounds=None, trunc: Optional[float] = None,
+                  min_alpha: float = 0.5, depth_max: Optional[float] = None, sharp: bool = True, batch: Optional[int] = None):
+        """Fuse the rendered depth (and colour) of `cameras` into a tsdf.TSDFVolume and return it (tsdf.py: the rule;
+        gs.tsdf_extract_mesh turns it into a mesh).  No gradient, eval mode, so the bilateral grid is never applied.
+        sharp: render every camera with sharp_outputs (fusing blurred depth would smear the surface); otherwise as
+        get_outputs_for_camera.  Pixels with accumulation >= min_alpha have weight 1, the rest 0.
+        volume None: a new one over `bounds` = (lo [3], hi [3]) — None: the box of the means between the 2nd and the 98th
+        percentile per axis, padded by 5 % of its size on every side — with cubic voxels sized so that the longest axis has
+        `resolution` samples.  trunc None: 4 voxels.  depth_max None: no far cut-off.  batch (None: tsdf.FRAMES_PER_LAUNCH)
+        views go into one tsdf_integrate call; cameras of another image size start a new call."""
+        from . import tsdf as T
+        cameras = list(cameras)
+        dev = self.means.device
+        if volume is None:
+            if bounds is None:
+                srt = self.means.detach().float().sort(dim=0).values
+                n = int(srt.shape[0])
+                lo, hi = srt[int(0.02 * (n - 1))], srt[int(math.ceil(0.98 * (n - 1)))]
+                pad = 0.05 * (hi - lo)
+                lo, hi = lo - pad, hi + pad
+            else:
+                lo, hi = (torch.as_tensor(b, dtype=torch.float32).reshape(3) for b in bounds)
+            lo, hi = [float(v) for v in lo.tolist()], [float(v) for v in hi.tolist()]
+            size = [h - l for l, h in zip(lo, hi)]
+            if int(resolution) < T.MIN_DIM or not all(math.isfinite(v) and v >= 0 for v in size) or max(size) <= 0:
+                raise ValueError(f"fuse_tsdf needs resolution >= {T.MIN_DIM} and a box of positive size, got {resolution}, {lo}, {hi}")
+            voxel = max(size) / (int(resolution) - 1)
+            dims = [min(T.MAX_DIM, max(T.MIN_DIM, int(math.ceil(v / voxel - 1e-6)) + 1)) for v in size]
+            volume = T.TSDFVolume(lo, voxel, dims, device=dev, color=True)
+        trunc = 4.0 * volume.voxel_size if trunc is None else float(trunc)
+        batch = T.FRAMES_PER_LAUNCH if batch is None else max(1, int(batch))
+        far = math.inf if depth_max is None else float(depth_max)
+        pending = []                                  # (depth [H,W], colour [H,W,3], weights [H,W], viewmat, intrin)
+
+        def flush():
+            if pending:
+                d, c, w, v, k = (torch.stack(col) for col in zip(*pending))
+                T.tsdf_integrate(volume, d, v, k, trunc, color=c if volume.color is not None else None, weights=w,
+                                 depth_max=far)
+                pending.clear()
+        for camera in cameras:
+            out = self.sharp_outputs(camera) if sharp else self.get_outputs_for_camera(camera)
+            if out.get("depth") is None:
+                raise ValueError("fuse_tsdf needs a render with depth")
+            depth = out["depth"].detach().float()
+            depth = depth[..., 0] if depth.dim() == 3 else depth
+            if pending and pending[0][0].shape != depth.shape:
+                flush()
+            viewmat = self._viewmat_and_velocity(camera)[0].detach().float()
+            acc = out["accumulation"].detach().float().reshape(depth.shape)
+            intrin = torch.tensor([camera.fx, camera.fy, camera.cx, camera.cy], dtype=torch.float32).to(dev)
+            pending.append((depth.contiguous(), out["rgb"].detach().float().clamp(0.0, 1.0), (acc >= float(min_alpha)).float(),
+                            viewmat, intrin))
+            if len(pending) >= batch:
+                flush()
+        flush()
+        return volume
 
     @torch.no_grad()
     def blur_stats(self, cameras, points: Optional[Tensor] = None):

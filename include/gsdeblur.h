@@ -876,6 +876,41 @@ int gs_depth_prior_loss(int B, int S, int H, int W, const float* depth_acc, cons
                         int kind, int space, float min_alpha, float weight, float* loss_out, double* stats_out,
                         float* v_depth_acc, float* v_alphas, void* ws, long long ws_bytes, void* stream);
 
+/* ---- TSDF fusion of depth maps and marching-tetrahedra mesh extraction (csrc/tsdf_math.h states the update rule, the
+ * tetrahedra and every order; tsdf.py drives it).  No allocation, no state, no atomics, no workgroup waits on another;
+ * two runs agree bit for bit.
+ *
+ * The volume: tsdf, weight [nz,ny,nx] fp32, color [nz,ny,nx,3] fp32 or NULL, x fastest; sample (i, j, k) sits at
+ * (ox, oy, oz) + voxel_size * (i, j, k).  2 <= nx, ny, nz <= 1024 and nx * ny * nz <= 2^30.
+ *
+ * gs_tsdf_integrate updates the volume in place from B frames: depth [B,H,W] camera-space z, viewmats [B,16] row-major
+ * world-to-camera (OpenCV axes, +z forward), intrins [B,4] = fx fy cx cy, color_images [B,H,W,3] (given exactly when
+ * color is), weight_images [B,H,W] or NULL (1).  Per voxel, frames in index order, fp32 without fused multiply-add:
+ * p = R x + t, skip if p.z <= 0; u = fx p.x / p.z + cx, v likewise, the pixel is (floor u, floor v), skip outside the
+ * image; D, w the pixel's depth and weight, skip unless D is finite, depth_min < D <= depth_max and w > 0;
+ * sdf = D - p.z, skip if sdf < -trunc; val = min(1, sdf / trunc); Wn = W + w; tsdf = (tsdf W + val w) / Wn, colour
+ * likewise; W = min(Wn, max_weight).  A voxel no frame touched is not written.  One launch per 16 frames; the result does
+ * not depend on how B is cut into calls.  B == 0 launches nothing.  H, W <= 16384, trunc > 0, max_weight > 0,
+ * voxel_size > 0; anything else, or a null pointer, is GS_ERR_INVALID before any launch.
+ *
+ * Extraction is two calls because V and F size the outputs.  gs_tsdf_mesh_count leaves V and F in counts (device, 2
+ * ints; -1: more than an int holds) and what gs_tsdf_mesh_emit needs in ws; the caller reads counts back, allocates
+ * verts [V,3] fp32, faces [F,3] int32 and colors [V,3] fp32 (NULL: not wanted; needs color) and calls
+ * gs_tsdf_mesh_emit with the same volume, level and ws.  A corner is inside when tsdf < level; a cell is used
+ * when its 8 corners have weight > min_weight.  Vertices are ordered by (owner sample, edge type), faces by (cell,
+ * tetrahedron, triangle); every vertex is referenced.  V == 0 and F == 0 launch nothing in emit.  ws: 256-byte aligned,
+ * gs_tsdf_mesh_workspace_bytes(nx, ny, nz) bytes (-1 on invalid arguments; a little over 6 bytes per sample). */
+int gs_tsdf_integrate(int nx, int ny, int nz, float ox, float oy, float oz, float voxel_size, float* tsdf, float* weight,
+                      float* color, int B, int H, int W, const float* depth, const float* viewmats, const float* intrins,
+                      const float* color_images, const float* weight_images, float trunc, float depth_min,
+                      float depth_max, float max_weight, void* stream);
+long long gs_tsdf_mesh_workspace_bytes(int nx, int ny, int nz);
+int gs_tsdf_mesh_count(int nx, int ny, int nz, const float* tsdf, const float* weight, float level, float min_weight,
+                       int* counts, void* ws, long long ws_bytes, void* stream);
+int gs_tsdf_mesh_emit(int nx, int ny, int nz, float ox, float oy, float oz, float voxel_size, const float* tsdf,
+                      const float* color, float level, int V, int F, float* verts, int* faces, float* colors, void* ws,
+                      long long ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
