@@ -26,11 +26,12 @@ from .ops import (  # noqa: F401
 )
 from .model import Camera, CameraShutterOptimizerConfig, SplatfactoDeblurConfig, SplatfactoDeblurModel  # noqa: F401
 from . import dp  # noqa: F401
-from . import bilagrid, blurscore, checkpoint, colorcorrect, data, densify, depthprior, fused, mcmc, step, train_step as training, tsdf  # noqa: F401
+from . import bilagrid, blurscore, checkpoint, colorcorrect, data, densify, depthprior, fused, mcmc, normals, step, train_step as training, tsdf  # noqa: F401
 from .colorcorrect import color_correct  # noqa: F401
 from .depthprior import depth_prior_loss, depth_prior_loss_with_grad  # noqa: F401
 from .knn import knn, knn_mean_distance  # noqa: F401
 from .tsdf import TSDFVolume, tsdf_integrate, tsdf_extract_mesh  # noqa: F401
+from .normals import depth_normals, normal_loss, normal_loss_with_grad  # noqa: F401
 from .blurscore import blur_stats  # noqa: F401
 from .step import render_step  # noqa: F401
 from .data import load_transforms, load_seed_points_ply  # noqa: F401

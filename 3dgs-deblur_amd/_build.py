@@ -37,6 +37,8 @@ SOURCES = [
     ("depthprior.hip", ["-ffp-contract=off"]),
     # TSDF fusion and mesh extraction (tsdf.py): the update rounds every operation, as the host build's does
     ("tsdf.hip", ["-ffp-contract=off"]),
+    # depth-derived normals, normal-prior and smoothness loss (normals.py): float32 values round every operation
+    ("normals.hip", ["-ffp-contract=off"]),
     ("frame.hip", []),           # host-side frame orchestration (no kernels of its own)
 ]
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-fvisibility=hidden"]

@@ -31,6 +31,9 @@ import torch
 from .model import Camera
 
 
+NORMAL_CONVENTIONS = ("opencv", "opengl")
+
+
 @dataclass
 class TransformsScene:
     cameras: List[Camera]
@@ -45,6 +48,10 @@ class TransformsScene:
     # per frame: the depth map's path (nerfstudio's depth_file_path) or None; [] for scenes built by hand
     depth_paths: List[Optional[str]] = field(default_factory=list)
     depth_unit_scale_factor: float = 1e-3
+    # per frame: the normal prior's path (normal_file_path) or None; normal_convention "opencv" (x right, y down, z
+    # forward: the frame of normals.depth_normals) or "opengl" (y and z negated on load)
+    normal_paths: List[Optional[str]] = field(default_factory=list)
+    normal_convention: str = "opencv"
 
 
 def split_indices(file_paths: List[str], eval_mode: str = "interval", eval_interval: int = 8,
@@ -91,7 +98,10 @@ def load_transforms(path: str, eval_mode: str = "interval", eval_interval: int =
     readout = float(meta.get("rolling_shutter_time", 0.0))
     s = 1.0 / float(downscale)
     W, H = int(round(meta["w"] * s)), int(round(meta["h"] * s))
-    cams, paths, dpaths = [], [], []
+    cams, paths, dpaths, npaths = [], [], [], []
+    convention = meta.get("normal_convention", "opencv")
+    if convention not in NORMAL_CONVENTIONS:
+        raise ValueError(f"transforms.json: unknown normal_convention {convention!r} (one of {NORMAL_CONVENTIONS})")
     is_eval_set = set()
     scores = None
     if eval_mode == "blur_score":
@@ -121,6 +131,8 @@ def load_transforms(path: str, eval_mode: str = "interval", eval_interval: int =
         paths.append(os.path.normpath(os.path.join(root, fr["file_path"])))
         dp = fr.get("depth_file_path")
         dpaths.append(os.path.normpath(os.path.join(root, dp)) if dp else None)
+        npth = fr.get("normal_file_path")
+        npaths.append(os.path.normpath(os.path.join(root, npth)) if npth else None)
     at = meta.get("applied_transform")
     return TransformsScene(
         cameras=cams, image_paths=paths, train_indices=tr, eval_indices=ev, exposure_time=exposure,
@@ -129,6 +141,7 @@ def load_transforms(path: str, eval_mode: str = "interval", eval_interval: int =
         ply_file_path=(os.path.normpath(os.path.join(root, meta["ply_file_path"])) if "ply_file_path" in meta else None),
         applied_transform=(torch.tensor(at, dtype=torch.float32) if at is not None else None),
         depth_paths=dpaths, depth_unit_scale_factor=float(meta.get("depth_unit_scale_factor", 1e-3)),
+        normal_paths=npaths, normal_convention=convention,
     )
 
 
@@ -296,6 +309,126 @@ def load_scene_depths(scene: "TransformsScene", device="cpu", undistort: bool = 
         elif lens:
             d, _ = undistort_depth(d, cam.fx, cam.fy, cam.cx, cam.cy, scene.distortion, crop=True)
         out.append(d)
+    return out
+
+
+def _read_png_rgb16(path: str):
+    """a non-interlaced 16-bit RGB(A) PNG -> uint16 [H,W,3], or None for any other file (PIL reads those; it would cut a
+    16-bit colour PNG to 8 bits).  Rows filtered with Average or Paeth are undone pixel by pixel in Python: slow, exact"""
+    import struct
+    import zlib
+    import numpy as np
+    with open(path, "rb") as f:
+        raw = f.read()
+    if raw[:8] != b"\x89PNG\r\n\x1a\n":
+        return None
+    pos, idat, head = 8, [], None
+    while pos + 8 <= len(raw):
+        n, kind = struct.unpack(">I4s", raw[pos:pos + 8])
+        body = raw[pos + 8:pos + 8 + n]
+        pos += 12 + n
+        if kind == b"IHDR":
+            head = struct.unpack(">IIBBBBB", body)
+        elif kind == b"IDAT":
+            idat.append(body)
+        elif kind == b"IEND":
+            break
+    if head is None or head[2] != 16 or head[3] not in (2, 6) or head[6] != 0:
+        return None
+    W, H, C = head[0], head[1], 3 if head[3] == 2 else 4
+    bpp, stride = 2 * C, 2 * C * W
+    data = np.frombuffer(zlib.decompress(b"".join(idat)), np.uint8).reshape(H, stride + 1)
+    out = np.zeros((H + 1, stride), np.uint8)
+    for y in range(H):
+        ft, row, up = int(data[y, 0]), data[y, 1:].astype(np.int64), out[y].astype(np.int64)
+        if ft == 0:
+            cur = row
+        elif ft == 2:
+            cur = row + up
+        elif ft == 1:
+            cur = np.cumsum(row.reshape(W, bpp), axis=0).reshape(-1)
+        elif ft in (3, 4):
+            cur = np.zeros(stride, np.int64)
+            for i in range(stride):
+                a = int(cur[i - bpp]) if i >= bpp else 0
+                b = int(up[i])
+                c = int(up[i - bpp]) if i >= bpp else 0
+                if ft == 3:
+                    pred = (a + b) // 2
+                else:
+                    pa, pb, pc = abs(b - c), abs(a - c), abs(a + b - 2 * c)
+                    pred = a if pa <= pb and pa <= pc else (b if pb <= pc else c)
+                cur[i] = (int(row[i]) + pred) & 255
+        else:
+            raise ValueError(f"{path}: PNG filter type {ft}")
+        out[y + 1] = (cur & 255).astype(np.uint8)
+    px = out[1:].reshape(H, W, C, 2).astype(np.uint16)
+    return (px[..., 0] << 8 | px[..., 1])[..., :3]
+
+
+def load_normal(path: str, convention: str = "opencv", device="cpu") -> torch.Tensor:
+    """[H,W,3] float32 normal map in the camera frame of normals.depth_normals (x right, y down, z forward).  `.npy`: a
+    float [H,W,3] array of vectors; an 8- or 16-bit RGB PNG: n = 2 v / max - 1 per channel.  convention "opengl" (x right, y
+    up, z towards the viewer): y and z are negated.  Vectors are not normalised here (the op does it); a non-finite vector
+    becomes the zero vector, "no value"."""
+    import numpy as np
+    if convention not in NORMAL_CONVENTIONS:
+        raise ValueError(f"unknown normal_convention {convention!r} (one of {NORMAL_CONVENTIONS})")
+    if path.endswith(".npy"):
+        arr = np.asarray(np.load(path), dtype=np.float64)
+    else:
+        px = _read_png_rgb16(path)
+        if px is None:
+            from PIL import Image
+            with Image.open(path) as im:
+                px = np.asarray(im.convert("RGB"))
+        arr = 2.0 * px.astype(np.float64) / float(np.iinfo(px.dtype).max) - 1.0
+    if arr.ndim != 3 or arr.shape[-1] != 3:
+        raise ValueError(f"{path}: a normal map must be [H,W,3], got shape {arr.shape}")
+    arr = arr.copy()
+    arr[~np.isfinite(arr).all(-1)] = 0.0
+    if convention == "opengl":
+        arr[..., 1:] *= -1.0
+    return torch.from_numpy(arr.astype(np.float32)).to(device)
+
+
+def undistort_normals(normals: torch.Tensor, fx: float, fy: float, cx: float, cy: float, distortion: Dict[str, float],
+                      crop: bool = False):
+    """undistort_depth for a normal map [H,W,3]: NEAREST-neighbour sampling, zero vectors for pixels that look outside the
+    source.  The vectors themselves are kept: the small rotation a lens undistortion implies for a direction is ignored."""
+    H, W = normals.shape[0], normals.shape[1]
+    if not _has_distortion(distortion):
+        return (normals, (0, 0, W, H)) if crop else normals
+    us, vs = _undistort_grid(H, W, fx, fy, cx, cy, distortion, normals.device)
+    ui, vi = torch.round(us).long(), torch.round(vs).long()
+    inside = (ui >= 0) & (ui < W) & (vi >= 0) & (vi < H)
+    out = torch.where(inside[..., None], normals[vi.clamp(0, H - 1), ui.clamp(0, W - 1)], torch.zeros((), dtype=normals.dtype))
+    out = out.to(normals.dtype).contiguous()
+    if not crop:
+        return out
+    x0, y0, x1, y1 = undistort_roi(H, W, fx, fy, cx, cy, distortion)
+    return out[y0:y1, x0:x1].contiguous(), (x0, y0, x1, y1)
+
+
+def load_scene_normals(scene: "TransformsScene", device="cpu", undistort: bool = True) -> List[Optional[torch.Tensor]]:
+    """every frame's normal prior [H,W,3] (load_normal with the scene's normal_convention), or None for a frame without
+    one — undistorted (nearest neighbour; the directions are not rotated, see undistort_normals) and cropped exactly like
+    load_scene_depths' maps."""
+    out: List[Optional[torch.Tensor]] = []
+    lens = undistort and _has_distortion(scene.distortion)
+    paths = scene.normal_paths or [None] * len(scene.cameras)
+    for cam, path in zip(scene.cameras, paths):
+        if path is None:
+            out.append(None)
+            continue
+        n = load_normal(path, scene.normal_convention, device)
+        if cam.metadata.get("undistorted", False):
+            x0, y0, x1, y1 = cam.metadata["undistort_roi"]
+            full = undistort_normals(n, cam.fx, cam.fy, cam.cx + x0, cam.cy + y0, scene.distortion) if lens else n
+            n = full[y0:y1, x0:x1].contiguous()
+        elif lens:
+            n, _ = undistort_normals(n, cam.fx, cam.fy, cam.cx, cam.cy, scene.distortion, crop=True)
+        out.append(n)
     return out
 
 

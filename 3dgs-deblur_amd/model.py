@@ -798,6 +798,20 @@ class SplatfactoDeblurModel(nn.Module):
         return volume
 
     @torch.no_grad()
+    def render_normals(self, camera: Camera, sharp: bool = True, min_alpha: float = 0.5) -> Tensor:
+        """[H,W,3] normals of the rendered depth of `camera` (normals.depth_normals: camera-frame unit vectors, x right, y
+        down, z forward, facing the camera; zeros where a pixel or one of its four neighbours has accumulation <=
+        min_alpha).  sharp: render with sharp_outputs, otherwise as get_outputs_for_camera.  No gradient, eval mode."""
+        from .normals import depth_normals
+        out = self.sharp_outputs(camera) if sharp else self.get_outputs_for_camera(camera)
+        if out.get("depth") is None:
+            raise ValueError("render_normals needs a render with depth")
+        H, W = int(camera.height), int(camera.width)
+        depth = out["depth"].detach().float().reshape(1, H, W)
+        m = (out["accumulation"].detach().float().reshape(1, H, W) > float(min_alpha)).float()
+        return depth_normals((depth * m).contiguous(), m, (camera.fx, camera.fy, camera.cx, camera.cy))
+
+    @torch.no_grad()
     def blur_stats(self, cameras, points: Optional[Tensor] = None):
         """blurscore.BlurStats of `cameras` (one entry per camera, in their order) over `points` [N,3] (default: the
         model's means): how many pixels each frame is smeared and sheared by, as THIS model renders it — every camera's

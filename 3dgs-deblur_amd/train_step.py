@@ -117,6 +117,57 @@ def depth_prior_term(depth: Tensor, accumulation: Tensor, prior: Tensor, kind: s
     return depth_prior_loss(depth.reshape(1, H, W) * m, m, prior.reshape(H, W), kind, space, weight)
 
 
+def downscale_normals(normals: Tensor, d: int) -> Tensor:
+    """[H,W,3] normal map (a zero or non-finite vector = no value) -> [H//d, W//d, 3]: per d x d block the mean of its VALID
+    vectors, renormalised; zero where the block holds none or they cancel (the normal counterpart of downscale_depth)"""
+    if d <= 1:
+        return normals
+    valid = torch.isfinite(normals).all(dim=-1, keepdim=True) & (normals != 0).any(dim=-1, keepdim=True)
+    x = torch.where(valid, normals, torch.zeros_like(normals)).permute(2, 0, 1)[None]
+    s = F.avg_pool2d(x, kernel_size=d, stride=d)[0].permute(1, 2, 0)
+    length = s.norm(dim=-1, keepdim=True)
+    return torch.where(length > 0, s / torch.clamp(length, min=1e-30), torch.zeros_like(s)).contiguous()
+
+
+def _check_normal_term(gt_normal, normal_lambda, normal_smooth_lambda, normal_edge_beta) -> None:
+    """train_step's normal keywords, checked before anything is launched"""
+    for name, v in (("normal_lambda", normal_lambda), ("normal_smooth_lambda", normal_smooth_lambda),
+                    ("normal_edge_beta", normal_edge_beta)):
+        if not (float(v) >= 0.0 and math.isfinite(float(v))):
+            raise ValueError(f"{name} must be a finite number >= 0, got {v}")
+    for g in (gt_normal if isinstance(gt_normal, (list, tuple)) else [gt_normal]):
+        if g is not None and not (isinstance(g, Tensor) and g.dim() == 3 and g.shape[-1] == 3):
+            raise ValueError(f"gt_normal must be a [H,W,3] tensor, got {tuple(g.shape) if isinstance(g, Tensor) else type(g)}")
+
+
+def _camera_intrins(model: SplatfactoDeblurModel, camera: Camera):
+    """fx, fy, cx, cy of the camera the frame is rendered with: the rescaled one under the resolution schedule"""
+    d = model.downscale_factor()
+    cam = camera.rescaled(d) if d > 1 else camera
+    return (cam.fx, cam.fy, cam.cx, cam.cy)
+
+
+def normal_term(depth: Tensor, accumulation: Tensor, intrins, prior: Optional[Tensor], guide: Optional[Tensor],
+                prior_weight: float, smooth_weight: float, edge_beta: float) -> Tensor:
+    """normals.normal_loss of a rendered depth map (autograd and batch routes): depth, accumulation [H,W,1], prior / guide
+    [H,W,3] or None; depth_acc = depth * m, alphas = m with m = (accumulation > 0), one sample, as depth_prior_term"""
+    from .normals import normal_loss
+    H, W = int(depth.shape[0]), int(depth.shape[1])
+    m = (accumulation > 0).to(depth.dtype).reshape(1, H, W)
+    return normal_loss(depth.reshape(1, H, W) * m, m, intrins, prior, guide, prior_weight if prior is not None else 0.0,
+                       smooth_weight, edge_beta)
+
+
+def _metric_depth_sums(depth_acc: Tensor, alphas: Tensor, gt_depth: Tensor, depth_lambda: float):
+    """the metric depth L1 as a loss on the compositor's raw sums: (loss, d loss / d depth_acc, d loss / d alphas) — what
+    render_and_backward builds for grad_depth, for a sums callable that also carries another term"""
+    from .model import expected_depth
+    da, al = depth_acc.detach().requires_grad_(True), alphas.detach().requires_grad_(True)
+    dl = _metric_depth_loss(expected_depth(da, al), gt_depth, depth_lambda)
+    v_acc, v_al = torch.autograd.grad(dl, (da, al), allow_unused=True)
+    return (dl.detach(), torch.zeros_like(da) if v_acc is None else v_acc, torch.zeros_like(al) if v_al is None else v_al)
+
+
 def scale_regularization(log_scales: Tensor, max_gauss_ratio: float = 10.0) -> Tensor:
     """Penalise needle-like Gaussians (PhysGaussian-style, as in splatfacto): mean(max(s_max/s_min, r) - r)."""
     s = torch.exp(log_scales)
@@ -335,7 +386,8 @@ def one_call_route(model: SplatfactoDeblurModel) -> bool:
 def train_step(model: SplatfactoDeblurModel, optimizers: Dict[str, torch.optim.Optimizer], camera: Camera,
                gt_image: Tensor, ssim_lambda: float = 0.2, allreduce: Optional[str] = None,
                gt_depth: Optional[Tensor] = None, depth_lambda: float = 0.0, depth_loss: Optional[str] = None,
-               depth_space: str = "depth") -> Dict[str, float]:
+               depth_space: str = "depth", gt_normal: Optional[Tensor] = None, normal_lambda: float = 0.0,
+               normal_smooth_lambda: float = 0.0, normal_edge_beta: float = 0.0) -> Dict[str, float]:
     """One training iteration: render (HIP) -> loss -> backward (HIP) -> [DP gradient all-reduce] -> Adam.
     camera / gt_image (/ gt_depth) may be lists: B cameras rendered as one batch (model.get_outputs_batch), the loss
     the mean over the cameras of the per-image loss, on the autograd route.
@@ -346,11 +398,21 @@ def train_step(model: SplatfactoDeblurModel, optimizers: Dict[str, torch.optim.O
     known up to scale and shift, depth_space="disparity" for one given as inverse depth.  On the one-call route the op
     takes the compositor's per-sample sums between the two halves (render_and_backward grad_depth_sums: no torch op for
     the depth term), on the autograd and batch routes the rendered depth map (depth_prior_term).  Unknown names raise
-    ValueError before anything is launched."""
+    ValueError before anything is launched.
+    gt_normal [H,W,3] (a normal PRIOR in the camera frame, x right, y down, z forward; a zero vector = no value) with
+    normal_lambda > 0, and / or normal_smooth_lambda > 0 (which needs no prior), add normals.normal_loss of the normals of
+    the rendered depth: normal_lambda * mean(1 - n.m) + normal_smooth_lambda * mean over adjacent pairs of
+    g (1 - n_p.n_q), with gt_image as the edge guide of g when normal_edge_beta > 0.  The op takes the intrinsics of the
+    camera the frame is rendered with and the prior follows the resolution schedule (downscale_normals).  On the one-call
+    route it runs on the raw sums through the same grad_depth_sums callable as the depth term (their gradients are added),
+    on the other routes on the rendered depth map (normal_term).  With every normal keyword at its default the step is
+    what it was, bit for bit."""
     _check_depth_prior(depth_loss, depth_space)
+    _check_normal_term(gt_normal, normal_lambda, normal_smooth_lambda, normal_edge_beta)
     if isinstance(camera, (list, tuple)):
         return _train_step_batch(model, optimizers, list(camera), list(gt_image), ssim_lambda, allreduce,
-                                 gt_depth, depth_lambda, depth_loss, depth_space)
+                                 gt_depth, depth_lambda, depth_loss, depth_space, gt_normal, normal_lambda,
+                                 normal_smooth_lambda, normal_edge_beta)
     depth_kind, depth_loss = depth_loss, _metric_depth_loss      # below, depth_loss is the module's function again
     model.train()
     for o in optimizers.values():
@@ -359,6 +421,12 @@ def train_step(model: SplatfactoDeblurModel, optimizers: Dict[str, torch.optim.O
     use_depth = gt_depth is not None and depth_lambda > 0
     if use_depth:
         gt_depth = downscale_depth(gt_depth.to(gt_image.device, torch.float32), model.downscale_factor())
+    use_prior = gt_normal is not None and normal_lambda > 0
+    use_normal = use_prior or normal_smooth_lambda > 0
+    if use_normal:
+        intrins = _camera_intrins(model, camera)
+        gt_normal = downscale_normals(gt_normal.to(gt_image.device, torch.float32), model.downscale_factor()) if use_prior else None
+        guide = gt_image if normal_edge_beta > 0 else None
     if one_call_route(model):
         # forward + backward of the frame as ONE host call (model.render_and_backward -> step.render_step): the HIP loss
         # kernel's forward already produces d loss / d rgb, so it sits between the two halves as a plain callable
@@ -385,7 +453,27 @@ def train_step(model: SplatfactoDeblurModel, optimizers: Dict[str, torch.optim.O
                 depth = depth.requires_grad_(True)
                 box["depth_loss"] = dl = depth_loss(depth, gt_depth, depth_lambda)
                 return torch.autograd.grad(dl, depth)[0]
-        if use_depth and depth_kind is not None:
+        if use_normal:
+            # the normal term starts from the raw sums too; a depth term that is on travels in the same callable, so that
+            # render_and_backward never sees both of its depth keywords
+            from .depthprior import depth_prior_loss_with_grad
+            from .normals import normal_loss_with_grad
+
+            def grad_depth_sums(depth_acc, alphas):
+                box["normal_loss"], v_acc, v_al = normal_loss_with_grad(
+                    depth_acc, alphas, intrins, gt_normal, guide, normal_lambda if use_prior else 0.0, normal_smooth_lambda,
+                    normal_edge_beta)
+                if use_depth and depth_kind is not None:
+                    box["depth_loss"], d_acc, d_al = depth_prior_loss_with_grad(
+                        depth_acc, alphas, gt_depth.reshape(gt_depth.shape[0], gt_depth.shape[1]), depth_kind, depth_space,
+                        depth_lambda)
+                elif use_depth:
+                    box["depth_loss"], d_acc, d_al = _metric_depth_sums(depth_acc, alphas, gt_depth, depth_lambda)
+                else:
+                    return v_acc, v_al
+                return d_acc + v_acc, d_al + v_al
+            rgb = model.render_and_backward(camera, grad_image, grad_depth_sums=grad_depth_sums)
+        elif use_depth and depth_kind is not None:
             # the prior loss starts from the compositor's raw sums: one kernel pair between the two halves, no torch op
             from .depthprior import depth_prior_loss_with_grad
             prior = gt_depth.reshape(gt_depth.shape[0], gt_depth.shape[1])
@@ -401,6 +489,8 @@ def train_step(model: SplatfactoDeblurModel, optimizers: Dict[str, torch.optim.O
         loss = box["loss"]
         if use_depth:
             loss = loss + box["depth_loss"].detach()
+        if use_normal:
+            loss = loss + box["normal_loss"].detach()
         if model.config.use_scale_regularization:
             reg = scale_regularization(model.scales)
             reg.backward()
@@ -417,7 +507,7 @@ def train_step(model: SplatfactoDeblurModel, optimizers: Dict[str, torch.optim.O
                 grids.grad = torch.zeros_like(grids)
             loss = loss + bilagrid.tv_fwd_bwd_hip(grids.detach(), float(model.config.bilateral_grid_tv_lambda), grids.grad)
     else:
-        out = model.get_outputs(camera, return_depth=True) if use_depth else model.get_outputs(camera)
+        out = model.get_outputs(camera, return_depth=True) if use_depth or use_normal else model.get_outputs(camera)
         rgb = out["rgb"].detach()
         loss = image_loss(out["rgb"], gt_image, ssim_lambda)
         if use_depth and depth_kind is not None:
@@ -425,6 +515,9 @@ def train_step(model: SplatfactoDeblurModel, optimizers: Dict[str, torch.optim.O
                                            depth_lambda)
         elif use_depth:
             loss = loss + depth_loss(out["depth"], gt_depth, depth_lambda)
+        if use_normal:
+            loss = loss + normal_term(out["depth"], out["accumulation"], intrins, gt_normal, guide, normal_lambda,
+                                      normal_smooth_lambda, normal_edge_beta)
         if model.config.use_scale_regularization:
             loss = loss + scale_regularization(model.scales)
         reg = _mcmc_reg(model)
@@ -458,11 +551,13 @@ def _dp_allreduce(model: SplatfactoDeblurModel, allreduce: str) -> None:
 
 def _train_step_batch(model: SplatfactoDeblurModel, optimizers, cameras, gt_images, ssim_lambda, allreduce,
                       gt_depths, depth_lambda, depth_loss: Optional[str] = None,
-                      depth_space: str = "depth") -> Dict[str, float]:
+                      depth_space: str = "depth", gt_normals=None, normal_lambda: float = 0.0,
+                      normal_smooth_lambda: float = 0.0, normal_edge_beta: float = 0.0) -> Dict[str, float]:
     """train_step for B cameras: one get_outputs_batch, loss = mean over the cameras of train_step's per-image loss
-    (image loss + optional depth loss; depth_loss / depth_space as train_step's), one autograd backward, one optimizer
-    step"""
+    (image loss + optional depth loss + optional normal loss; the keywords as train_step's, gt_normals a list with None
+    for a camera without a prior), one autograd backward, one optimizer step"""
     _check_depth_prior(depth_loss, depth_space)
+    _check_normal_term(gt_normals, normal_lambda, normal_smooth_lambda, normal_edge_beta)
     depth_kind, depth_loss = depth_loss, _metric_depth_loss      # below, depth_loss is the module's function again
     if len(cameras) != len(gt_images) or not cameras:
         raise ValueError("train_step needs as many images as cameras")
@@ -474,10 +569,19 @@ def _train_step_batch(model: SplatfactoDeblurModel, optimizers, cameras, gt_imag
     use_depth = gt_depths is not None and depth_lambda > 0
     if use_depth:
         gt_depths = [None if g is None else downscale_depth(g.to(gts[0].device, torch.float32), d) for g in gt_depths]
-    out = model.get_outputs_batch(cameras, return_depth=True) if use_depth else model.get_outputs_batch(cameras)
+    use_prior = gt_normals is not None and normal_lambda > 0
+    use_normal = use_prior or normal_smooth_lambda > 0
+    if use_prior:
+        gt_normals = [None if g is None else downscale_normals(g.to(gts[0].device, torch.float32), d) for g in gt_normals]
+    out = model.get_outputs_batch(cameras, return_depth=True) if use_depth or use_normal else model.get_outputs_batch(cameras)
     losses = []
     for b in range(len(cameras)):
         l_b = image_loss(out["rgb"][b], gts[b], ssim_lambda)
+        prior_b = gt_normals[b] if use_prior else None
+        if use_normal and (prior_b is not None or normal_smooth_lambda > 0):
+            l_b = l_b + normal_term(out["depth"][b], out["accumulation"][b], _camera_intrins(model, cameras[b]), prior_b,
+                                    gts[b] if normal_edge_beta > 0 else None, normal_lambda, normal_smooth_lambda,
+                                    normal_edge_beta)
         if use_depth and gt_depths[b] is not None and depth_kind is not None:
             l_b = l_b + depth_prior_term(out["depth"][b], out["accumulation"][b], gt_depths[b], depth_kind, depth_space,
                                          depth_lambda)
@@ -574,13 +678,16 @@ def train_scene(model: SplatfactoDeblurModel, scene, images, iterations: int, lr
                 ssim_lambda: float = 0.2, optimize_eval_cameras: bool = False, eval_camera_every: int = 4,
                 densify=None, log_every: int = 0, seed: int = 0, depths=None, depth_lambda: float = 0.0,
                 batch_size: int = 1, optimizer: Optional[str] = None, checkpoint_path=None, checkpoint_every: int = 0,
-                resume=None, depth_loss: Optional[str] = None, depth_space: str = "depth") -> Dict:
+                resume=None, depth_loss: Optional[str] = None, depth_space: str = "depth", normals=None,
+                normal_lambda: float = 0.0, normal_smooth_lambda: float = 0.0, normal_edge_beta: float = 0.0) -> Dict:
     """Train on scene.train_indices (one view per step, seeded shuffle), optionally refining the evaluation cameras
     in between; returns {'results': {psnr, ssim}, 'wall_clock_time_seconds', 'history'} like the reference's
     metrics.json (/root/reference/train.py:87-100, parse_outputs.py:58); with config.color_corrected_metrics the results
     also carry cc_psnr / cc_ssim (evaluate).  depths (optional): per-frame depth maps
     [H,W,1] or None, indexed like images (data.load_depth); with depth_lambda > 0 every step adds the depth loss.
     depth_loss / depth_space: train_step's — "pearson" (or "l1") takes the maps as depth PRIORS (depthprior).
+    normals (optional): per-frame normal priors [H,W,3] or None, indexed like images (data.load_scene_normals), used with
+    normal_lambda > 0; normal_smooth_lambda / normal_edge_beta: train_step's (the smoothness term needs no prior).
     batch_size > 1: every step takes that many views of the shuffle (fewer at the end of a pass) as one batch
     (train_step with lists), and the evaluation renders in batches of that size.  optimizer: make_optimizers' choice
     ("adam" / "selective_adam"; default model.config.optimizer).  densify: a densify.DensifyConfig (splatfacto's split /
@@ -596,6 +703,8 @@ def train_scene(model: SplatfactoDeblurModel, scene, images, iterations: int, lr
     from . import mcmc as M
     use_mcmc = isinstance(densify, M.MCMCConfig)
     _check_depth_prior(depth_loss, depth_space)
+    _check_normal_term(None, normal_lambda, normal_smooth_lambda, normal_edge_beta)
+    normal_kw = dict(normal_lambda=normal_lambda, normal_smooth_lambda=normal_smooth_lambda, normal_edge_beta=normal_edge_beta)
     if checkpoint_every and checkpoint_path is None:
         raise ValueError("checkpoint_every needs checkpoint_path")
     loaded = None
@@ -658,13 +767,17 @@ def train_scene(model: SplatfactoDeblurModel, scene, images, iterations: int, lr
         if batch_size > 1:
             ids = [order.pop() for _ in range(min(batch_size, len(order)))]
             gd = [depths[i] for i in ids] if depths is not None else None
+            gn = [normals[i] for i in ids] if normals is not None else None
             h = train_step(model, optimizers, [scene.cameras[i] for i in ids], [images[i] for i in ids], ssim_lambda,
-                           gt_depth=gd, depth_lambda=depth_lambda, depth_loss=depth_loss, depth_space=depth_space)
+                           gt_depth=gd, depth_lambda=depth_lambda, depth_loss=depth_loss, depth_space=depth_space,
+                           gt_normal=gn, **normal_kw)
         else:
             i = order.pop()
             gd = depths[i] if depths is not None else None
+            gn = normals[i] if normals is not None else None
             h = train_step(model, optimizers, scene.cameras[i], images[i], ssim_lambda, gt_depth=gd,
-                           depth_lambda=depth_lambda, depth_loss=depth_loss, depth_space=depth_space)
+                           depth_lambda=depth_lambda, depth_loss=depth_loss, depth_space=depth_space, gt_normal=gn,
+                           **normal_kw)
         if use_mcmc:
             M.step_callback(model, optimizers, it, densify)
         elif densify is not None:

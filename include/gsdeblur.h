@@ -911,6 +911,41 @@ int gs_tsdf_mesh_emit(int nx, int ny, int nz, float ox, float oy, float oz, floa
                       const float* color, float level, int V, int F, float* verts, int* faces, float* colors, void* ws,
                       long long ws_bytes, void* stream);
 
+/* ---- normals from the rendered depth, normal-prior and normal smoothness loss (csrc/normal_math.h states every formula;
+ * normals.py drives it).  No allocation, no state, no atomics, nothing read back; two runs agree bit for bit and a
+ * frame's results do not depend on the rest of the batch.
+ *
+ * depth_acc, alphas [B,S,H,W] fp32: the compositor's per-sample sums, d and a their sample means as in
+ * gs_depth_prior_loss.  intrins [B,4] fp32 (device) = fx fy cx cy of the camera each frame was rendered with.  Per pixel
+ * (u, v), in fp32 without fused multiply-add: has_z iff a > min_alpha and d > 0, z = d / a, P = (rx z, ry z, z) with
+ * rx = ((u + 0.5) - cx) / fx, ry = ((v + 0.5) - cy) / fy.  A pixel with 1 <= u <= W - 2, 1 <= v <= H - 2 whose own has_z
+ * and that of its four axis neighbours hold has tx = P(u+1,v) - P(u-1,v), ty = P(u,v+1) - P(u,v-1), c = ty x tx,
+ * l2 = c.c, and, iff l2 > 1e-30f, the normal n = c / sqrt(l2): camera frame (x right, y down, z forward), facing the
+ * camera.  normals_out [B,H,W,3] fp32 receives it, (0,0,0) where there is none.
+ *
+ * gs_depth_normals: that, in one launch.
+ *
+ * gs_normal_loss: two launches.  prior [B,H,W,3] fp32 or NULL: a pixel whose vector has a squared length that is 0 or not
+ * finite in fp32 has no value; the others are normalised, m.  guide [B,H,W,3] fp32 or NULL (ignored with edge_beta == 0).
+ * Over frame b in float64, in an order fixed by H and W: Np pixels with a normal and a prior value and their sum of
+ * 1 - n.m; Ns horizontally or vertically adjacent pairs (p, q) of normals, their sum of g (1 - n_p.n_q) and of g, with
+ * g = exp(-edge_beta (|dI_r| + |dI_g| + |dI_b|) / 3) of the guide in fp32, or 1.
+ * loss_out[b] = prior_weight sum(1 - n.m) / max(Np, 1) + smooth_weight sum g (1 - n_p.n_q) / max(Ns, 1).
+ * stats_out [B*6] float64: the number of normals, Np, sum(1 - n.m), Ns, sum g (1 - n_p.n_q), sum g.
+ * v_depth_acc, v_alphas [B,S,H,W] receive d loss_out[b] / d depth_acc, d alphas (float64 chain, rounded once; the same
+ * value for every sample of a pixel; exact zeros at pixels without has_z and for a term whose count is 0).
+ * normals_out may be NULL.  1 <= S, B * S <= 256, H, W >= 1, B * S * H * W < 2^30, min_alpha >= 0, edge_beta >= 0;
+ * anything else, or a null pointer where none is allowed, is GS_ERR_INVALID before any launch.  B == 0 launches nothing.
+ * ws: 8-byte aligned, gs_normal_loss_workspace_bytes(B, S, H, W) bytes (-1 on invalid arguments; 20 bytes per pixel and
+ * 48 bytes per frame and 256 x 8 pixels). */
+int gs_depth_normals(int B, int S, int H, int W, const float* depth_acc, const float* alphas, const float* intrins,
+                     float min_alpha, float* normals_out, void* stream);
+long long gs_normal_loss_workspace_bytes(int B, int S, int H, int W);
+int gs_normal_loss(int B, int S, int H, int W, const float* depth_acc, const float* alphas, const float* intrins,
+                   const float* prior, const float* guide, float prior_weight, float smooth_weight, float edge_beta,
+                   float min_alpha, float* loss_out, double* stats_out, float* normals_out, float* v_depth_acc,
+                   float* v_alphas, void* ws, long long ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

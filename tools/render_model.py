@@ -11,7 +11,9 @@ adjustment a checkpoint carries), model.get_outputs_for_camera renders it, and <
 pred/depth/raw/<stem>.npy are written (the reference's names, render_model.py:101-104, 127-133).  metrics.json holds
 {"results": {"psnr", "ssim"}} with training.evaluate's formulas; --color-correct adds <stem>_cc.png (the render after
 gs.color_correct fitted its colours to the image) and cc_psnr / cc_ssim.  A PLY carries no camera-side parameters and no
-training config: it renders with the defaults at the file's SH degree and --blur-samples (default 0: one sharp render)."""
+training config: it renders with the defaults at the file's SH degree and --blur-samples (default 0: one sharp render).
+--normals also writes the normals of the sharp render's depth (model.render_normals): <stem>_normal.png, the usual
+picture (n * (1, -1, -1) + 1) / 2 with pixels without a normal black, and normal/<stem>.npy, the camera-frame vectors."""
 import argparse
 import json
 import os
@@ -25,7 +27,7 @@ sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 import gsdeblur_amd as gs  # noqa: E402
 
 
-def main():
+def build_parser():
     ap = argparse.ArgumentParser()
     src = ap.add_mutually_exclusive_group(required=True)
     src.add_argument("--checkpoint", default=None)
@@ -38,7 +40,21 @@ def main():
     ap.add_argument("--color-correct", action="store_true",
                     help="also write <stem>_cc.png, the render fitted to its image by gs.color_correct, and cc_psnr / "
                          "cc_ssim into metrics.json")
-    args = ap.parse_args()
+    ap.add_argument("--normals", action="store_true",
+                    help="also write <stem>_normal.png and normal/<stem>.npy: the normals of the sharp render's depth")
+    ap.add_argument("--normal-min-alpha", type=float, default=0.5,
+                    help="--normals: pixels whose accumulation is not above it have no depth, hence no normal")
+    return ap
+
+
+def normal_picture(normals):
+    """[H,W,3] camera-frame normals -> the usual picture: (n * (1, -1, -1) + 1) / 2, pixels without a normal black"""
+    has = (normals != 0).any(dim=-1, keepdim=True)
+    return torch.where(has, (normals * normals.new_tensor([1.0, -1.0, -1.0]) + 1.0) * 0.5, torch.zeros_like(normals))
+
+
+def main():
+    args = build_parser().parse_args()
     dev = torch.device(args.device)
     scene = gs.load_transforms(args.data)
     images = gs.data.load_scene_images(scene, dev)
@@ -51,6 +67,8 @@ def main():
         model = gs.SplatfactoDeblurModel.from_ply(args.ply, cfg, dev, num_cameras=len(scene.cameras))
     indices = scene.eval_indices if args.set == "eval" else scene.train_indices
     os.makedirs(os.path.join(args.out, "pred", "depth", "raw"), exist_ok=True)
+    if args.normals:
+        os.makedirs(os.path.join(args.out, "normal"), exist_ok=True)
     ps, ss, cps, css = [], [], [], []
     for i in indices:
         camera = scene.cameras[i]
@@ -61,6 +79,10 @@ def main():
         gs.data.save_image(os.path.join(args.out, f"{stem}_pred.png"), rgb)
         gs.data.save_image(os.path.join(args.out, f"{stem}_gt.png"), images[i])
         np.save(os.path.join(args.out, "pred", "depth", "raw", f"{stem}.npy"), depth.detach().cpu().numpy())
+        if args.normals:
+            normals = model.render_normals(camera, min_alpha=args.normal_min_alpha)
+            gs.data.save_image(os.path.join(args.out, f"{stem}_normal.png"), normal_picture(normals))
+            np.save(os.path.join(args.out, "normal", f"{stem}.npy"), normals.cpu().numpy())
         ps.append(gs.training.psnr(rgb, images[i]))
         ss.append(float(gs.training.ssim(rgb.clamp(0, 1), images[i]).item()))
         if args.color_correct:

@@ -12,7 +12,8 @@ touching the Gaussians (train.py:180-183); --densify adds splatfacto's refinemen
 --bilateral-grid learns a per-image colour correction with the scene; --color-corrected-metrics adds cc_psnr / cc_ssim
 (the evaluation renders fitted to their images by a quadratic colour warp first); --optimize-exposure / --optimize-readout learn the
 exposure and rolling-shutter readout times from their metadata values; --depth-lambda adds a depth term on the dataset's
-depth maps (--depth-loss pearson: monocular priors known up to scale and shift).  Every variant leaves checkpoint_<name>.pt beside
+depth maps (--depth-loss pearson: monocular priors known up to scale and shift); --normal-lambda / --normal-smooth-lambda add
+the normal-prior and normal smoothness terms on the normals of the rendered depth.  Every variant leaves checkpoint_<name>.pt beside
 its metrics_<name>.json (--checkpoint-every K: also every K steps; --resume PATH continues from one; --export-ply adds
 splat_<name>.ply for a viewer); tools/render_model.py renders either file."""
 import argparse
@@ -85,6 +86,16 @@ def build_parser():
     ap.add_argument("--depth-space", default="depth", choices=["depth", "disparity"],
                     help="--depth-loss l1 / pearson: compare the rendered depth, or its inverse (a prior given as inverse "
                          "depth, as MiDaS and Depth Anything give it)")
+    ap.add_argument("--normal-lambda", type=float, default=0.0,
+                    help="weight of the normal-prior term mean(1 - n.m) on the normals of the rendered depth; > 0 loads "
+                         "the maps the dataset's normal_file_path entries name (data.load_scene_normals; camera frame, "
+                         "the dataset's normal_convention)")
+    ap.add_argument("--normal-smooth-lambda", type=float, default=0.0,
+                    help="weight of the normal smoothness term, the mean over adjacent pixel pairs of g (1 - n_p.n_q); "
+                         "needs no prior")
+    ap.add_argument("--normal-edge-beta", type=float, default=0.0,
+                    help="g = exp(-beta * mean |dI|) of the training image relaxes the smoothness term across image "
+                         "edges; 0: g = 1")
     ap.add_argument("--out", default="gpurun_out/deblur")
     return ap
 
@@ -107,6 +118,11 @@ def main():
         depths = gs.data.load_scene_depths(scene, dev)           # follows the images' undistortion and crop; None where absent
         if all(d is None for d in depths):
             ap.error("--depth-lambda > 0, but no frame of the dataset names a depth_file_path")
+    normals = None
+    if args.normal_lambda > 0:
+        normals = gs.data.load_scene_normals(scene, dev)         # as the depth maps: undistorted nearest-neighbour, cropped
+        if all(n is None for n in normals):
+            ap.error("--normal-lambda > 0, but no frame of the dataset names a normal_file_path")
     if args.random_init <= 0:
         if not scene.ply_file_path:
             ap.error("the dataset names no seed cloud (ply_file_path): give --random-init N")
@@ -157,7 +173,9 @@ def main():
                                       densify=dcfg, checkpoint_path=os.path.join(args.out, f"checkpoint_{name}.pt"),
                                       checkpoint_every=args.checkpoint_every, resume=resume, depths=depths,
                                       depth_lambda=args.depth_lambda, depth_loss=args.depth_loss,
-                                      depth_space=args.depth_space)
+                                      depth_space=args.depth_space, normals=normals, normal_lambda=args.normal_lambda,
+                                      normal_smooth_lambda=args.normal_smooth_lambda,
+                                      normal_edge_beta=args.normal_edge_beta)
         if args.export_ply:
             gs.checkpoint.export_ply(os.path.join(args.out, f"splat_{name}.ply"), model)
         with open(os.path.join(args.out, f"metrics_{name}.json"), "wt") as f:
