@@ -4,56 +4,28 @@
 //
 // Two launches, nothing is read back between them:
 //   1. moments: grid (tiles of kTile pixels, B).  Thread t takes pixels t, t + kThreads, ... of its tile: the 2 S planes
-//      and the prior are read plane-wise, coalesced.  Its seven float64 moments are added over the 64 lanes in a butterfly,
-//      lane 0 leaves them in LDS, thread k < 7 adds the waves' moment k in wave order and stores it: one record per tile;
-//   2. gradient: the same grid.  Every workgroup first adds its frame's records — thread t records t, t + kThreads, ... in
-//      order, then the same wave / LDS reduction, so all workgroups of a frame hold the same bits — derives the float64
+//      and the prior are read plane-wise, coalesced.  The threads' seven float64 moments are added by sums_loss.h's
+//      block_add (butterfly, then the waves in wave order) and stored: one record per tile;
+//   2. gradient: the same grid.  Every workgroup first adds its frame's records (sums_loss.h frame_sum: thread t records
+//      t, t + kThreads, ... in order, then block_add, so all workgroups of a frame hold the same bits), derives the float64
 //      coefficients, RE-READS the 2 S planes of its tile (DESIGN 5.13 says why they are not stashed) and stores the 2 S
 //      gradient planes.  Workgroup 0 of a frame also stores loss[b] and stats[b][8].
 // No atomics; the order of every sum depends on H * W alone, so two runs agree bit for bit and a frame's result does not
 // depend on what else is in the batch.
-#include "gs_common.h"
+#include "sums_loss.h"
 #include "depthprior_math.h"
 
 namespace {
 
 namespace dp = gs::depthprior;
+namespace sums = gs::sums;
 
 constexpr int kThreads = 256;
 constexpr int kTile = 4096;                       // pixels per workgroup: 16 per thread, 507 tiles for a 1080p frame
 constexpr int kWaves = kThreads / gs::kWave;
-constexpr int kMaxPlanes = 256;                   // B * S
-constexpr long long kMaxElems = 1LL << 30;        // B * S * H * W stays below it
 
 static_assert(kTile % kThreads == 0 && kThreads % gs::kWave == 0 && dp::kMoments <= kThreads, "layout");
 static_assert(sizeof(dp::Moments) == dp::kMoments * sizeof(double), "records are 7 doubles");
-
-__device__ __forceinline__ void wave_add(dp::Moments& a) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    dp::Moments b;
-    b.n = __shfl_xor(a.n, o); b.sx = __shfl_xor(a.sx, o); b.sy = __shfl_xor(a.sy, o); b.sxx = __shfl_xor(a.sxx, o);
-    b.syy = __shfl_xor(a.syy, o); b.sxy = __shfl_xor(a.sxy, o); b.sabs = __shfl_xor(a.sabs, o);
-    dp::add_moments(a, b);
-  }
-}
-
-// every thread's moments -> the workgroup's, in part[0 .. kMoments) (valid after the call for every thread)
-__device__ __forceinline__ void block_add(dp::Moments a, double* wave_part, double* part) {
-  wave_add(a);
-  const int t = (int)threadIdx.x;
-  if (gs::lane_id() == 0) {
-    double* w = wave_part + (t / gs::kWave) * dp::kMoments;
-    w[0] = a.n; w[1] = a.sx; w[2] = a.sy; w[3] = a.sxx; w[4] = a.syy; w[5] = a.sxy; w[6] = a.sabs;
-  }
-  __syncthreads();
-  if (t < dp::kMoments) {
-    double sum = wave_part[t];
-    for (int w = 1; w < kWaves; ++w) sum += wave_part[w * dp::kMoments + t];
-    part[t] = sum;
-  }
-  __syncthreads();
-}
 
 // records [B][tiles][kMoments]
 __global__ __launch_bounds__(kThreads) void depth_prior_moments_kernel(int S, int pixels, int tiles, int kind, int space,
@@ -80,7 +52,7 @@ __global__ __launch_bounds__(kThreads) void depth_prior_moments_kernel(int S, in
       dp::add_pixel(m, valid, x, y, kind);
     }
   }
-  block_add(m, wave_part, part);
+  sums::block_add<kWaves>(m, wave_part, part);
   if (t < dp::kMoments) records[((size_t)b * tiles + tile) * dp::kMoments + t] = part[t];
 }
 
@@ -96,12 +68,8 @@ __global__ __launch_bounds__(kThreads) void depth_prior_grad_kernel(int S, int p
   __shared__ double wave_part[kWaves * dp::kMoments];
   __shared__ double part[dp::kMoments];
   const int t = (int)threadIdx.x, tile = (int)blockIdx.x, b = (int)blockIdx.y;
-  dp::Moments m;
-  dp::clear_moments(m);
-  const dp::Moments* rec = reinterpret_cast<const dp::Moments*>(records) + (size_t)b * tiles;
-  for (int r = t; r < tiles; r += kThreads) dp::add_moments(m, rec[r]);
-  block_add(m, wave_part, part);
-  m.n = part[0]; m.sx = part[1]; m.sy = part[2]; m.sxx = part[3]; m.syy = part[4]; m.sxy = part[5]; m.sabs = part[6];
+  const dp::Moments m = sums::frame_sum<kThreads>(reinterpret_cast<const dp::Moments*>(records) + (size_t)b * tiles, tiles,
+                                                 wave_part, part);
   const dp::Coef c = dp::finish(m, kind, (double)weight);
   if (tile == 0 && t == 0) {
     loss[b] = (float)c.loss;
@@ -118,19 +86,9 @@ __global__ __launch_bounds__(kThreads) void depth_prior_grad_kernel(int S, int p
       const float y = prior[(size_t)b * pixels + p];
       float x, vd = 0.0f, va = 0.0f;
       if (dp::pixel_x(d, a, y, space, min_alpha, &x) && !c.degenerate) dp::chain(dp::grad_x(c, x, y), d, a, space, S, &vd, &va);
-      for (int s = 0; s < S; ++s) {
-        v_depth_acc[frame + (size_t)s * pixels + p] = vd;
-        v_alphas[frame + (size_t)s * pixels + p] = va;
-      }
+      sums::store_pair(v_depth_acc, v_alphas, frame, (size_t)pixels, (size_t)p, S, vd, va);
     }
   }
-}
-
-bool shape_ok(int B, int S, int H, int W) {
-  if (B < 0 || S < 1 || H < 1 || W < 1) return false;
-  if ((long long)B * S > kMaxPlanes) return false;
-  const long long pixels = (long long)H * W;
-  return pixels < kMaxElems && (long long)(B > 0 ? B : 1) * S * pixels < kMaxElems;
 }
 
 int tiles_of(long long pixels) { return (int)((pixels + kTile - 1) / kTile); }
@@ -139,7 +97,7 @@ int tiles_of(long long pixels) { return (int)((pixels + kTile - 1) / kTile); }
 
 // see include/gsdeblur.h
 GS_EXPORT long long gs_depth_prior_workspace_bytes(int B, int S, int H, int W) {
-  if (!shape_ok(B, S, H, W)) return -1;
+  if (!sums::shape_ok(B, S, H, W)) return -1;
   return (long long)B * tiles_of((long long)H * W) * (long long)sizeof(dp::Moments);
 }
 
@@ -148,13 +106,14 @@ GS_EXPORT int gs_depth_prior_loss(int B, int S, int H, int W, const float* depth
                                   const float* prior, int kind, int space, float min_alpha, float weight, float* loss_out,
                                   double* stats_out, float* v_depth_acc, float* v_alphas, void* ws, long long ws_bytes,
                                   void* stream) {
-  if (!shape_ok(B, S, H, W)) return GS_ERR_INVALID;
+  if (!sums::shape_ok(B, S, H, W)) return GS_ERR_INVALID;
   if ((kind != dp::kPearson && kind != dp::kL1) || (space != dp::kDepth && space != dp::kDisparity)) return GS_ERR_INVALID;
   if (!(min_alpha >= 0.0f) || !(weight == weight)) return GS_ERR_INVALID;
   if (B == 0) return GS_OK;
-  if (!depth_acc || !alphas || !prior || !loss_out || !stats_out || !v_depth_acc || !v_alphas || !ws) return GS_ERR_INVALID;
-  if (((uintptr_t)ws & 7) || ((uintptr_t)stats_out & 7)) return GS_ERR_INVALID;
-  if (ws_bytes < gs_depth_prior_workspace_bytes(B, S, H, W)) return GS_ERR_WORKSPACE;
+  if (!prior) return GS_ERR_INVALID;
+  const int ok = sums::check_loss_call(depth_acc, alphas, loss_out, stats_out, v_depth_acc, v_alphas, ws, ws_bytes,
+                                       gs_depth_prior_workspace_bytes(B, S, H, W));
+  if (ok != GS_OK) return ok;
   const int pixels = H * W, tiles = tiles_of(pixels);
   hipStream_t st = (hipStream_t)stream;
   double* records = reinterpret_cast<double*>(ws);

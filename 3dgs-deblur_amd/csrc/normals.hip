@@ -8,21 +8,22 @@
 //   1. forward: the 2 S planes are read once per pixel over tile + 2 rings and reduced to the sample means d, a; normals on
 //      tile + 1 ring; the tile's normals are stored, and (d, a) are stashed as one float2 per pixel (DESIGN 5.15 says why);
 //      every thread adds the prior term of its pixel and the pairs its pixel owns (q = p + x, p + y) to six float64 sums,
-//      which are added over the 64 lanes in a butterfly, over the waves in wave order: one record per workgroup;
-//   2. gradient: the same grid.  Every workgroup first adds its frame's records — thread t records t, t + kThreads, ... in
-//      order, then the same reduction, so all workgroups of a frame hold the same bits — and derives the coefficients;
-//      per tile it loads (d, a) and the stored normals over tile + 2 rings, rebuilds v_n, v_tx, v_ty on tile + 1 ring
-//      (float64, in LDS), gathers v_z for its pixel and stores the 2 S gradient planes.  Workgroup 0 of a frame also
-//      stores loss[b] and stats[b][6].
+//      which sums_loss.h's block_add adds (butterfly, then the waves in wave order): one record per workgroup;
+//   2. gradient: the same grid.  Every workgroup first adds its frame's records (sums_loss.h frame_sum: thread t records
+//      t, t + kThreads, ... in order, then block_add, so all workgroups of a frame hold the same bits) and derives the
+//      coefficients; per tile it loads (d, a) and the stored normals over tile + 2 rings, rebuilds v_n, v_tx, v_ty on
+//      tile + 1 ring (float64, in LDS), gathers v_z for its pixel and stores the 2 S gradient planes.  Workgroup 0 of a
+//      frame also stores loss[b] and stats[b][6].
 // gs_depth_normals is launch 1 without the sums and the stash.  No atomics; the order of every sum depends on H and W
 // alone, so two runs agree bit for bit and a frame's result does not depend on what else is in the batch.
-#include "gs_common.h"
+#include "sums_loss.h"
 #include "normal_math.h"
 
 namespace {
 
 namespace nm = gs::normal;
 namespace dp = gs::depthprior;
+namespace sums = gs::sums;
 
 constexpr int kTileW = 32;
 constexpr int kTileH = 8;
@@ -31,38 +32,9 @@ constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / gs::kWave;
 constexpr int kHaloW = kTileW + 4, kHaloH = kTileH + 4;      // tile + 2 rings
 constexpr int kRingW = kTileW + 2, kRingH = kTileH + 2;      // tile + 1 ring
-constexpr int kMaxPlanes = 256;                   // B * S
-constexpr long long kMaxElems = 1LL << 30;        // B * S * H * W stays below it
 
 static_assert(kThreads == kTileW * kTileH && kThreads % gs::kWave == 0 && nm::kStats <= kThreads, "layout");
 static_assert(sizeof(nm::Sums) == nm::kStats * sizeof(double), "records are 6 doubles");
-
-__device__ __forceinline__ void wave_add(nm::Sums& a) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    nm::Sums b;
-    b.n_def = __shfl_xor(a.n_def, o); b.np = __shfl_xor(a.np, o); b.sp = __shfl_xor(a.sp, o);
-    b.ns = __shfl_xor(a.ns, o); b.ss = __shfl_xor(a.ss, o); b.sg = __shfl_xor(a.sg, o);
-    nm::add_sums(a, b);
-  }
-}
-
-// every thread's sums -> the workgroup's, in part[0 .. kStats) (valid after the call for every thread)
-__device__ __forceinline__ void block_add(nm::Sums a, double* wave_part, double* part) {
-  wave_add(a);
-  const int t = (int)threadIdx.x;
-  if (gs::lane_id() == 0) {
-    double* w = wave_part + (t / gs::kWave) * nm::kStats;
-    w[0] = a.n_def; w[1] = a.np; w[2] = a.sp; w[3] = a.ns; w[4] = a.ss; w[5] = a.sg;
-  }
-  __syncthreads();
-  if (t < nm::kStats) {
-    double sum = wave_part[t];
-    for (int w = 1; w < kWaves; ++w) sum += wave_part[w * nm::kStats + t];
-    part[t] = sum;
-  }
-  __syncthreads();
-}
 
 struct Frame {
   int S, H, W, groups_x;
@@ -134,7 +106,7 @@ __global__ __launch_bounds__(kThreads) void normal_fwd_kernel(Frame f, const flo
     }
   }
   if (kLoss) {
-    block_add(m, wave_part, part);
+    sums::block_add<kWaves>(m, wave_part, part);
     if (t < nm::kStats) records[((size_t)b * gridDim.x + blockIdx.x) * nm::kStats + t] = part[t];
   }
 }
@@ -160,12 +132,8 @@ __global__ __launch_bounds__(kThreads) void normal_grad_kernel(Frame f, float pr
   const int H = f.H, W = f.W, S = f.S;
   const size_t pixels = (size_t)H * (size_t)W, frame = (size_t)b * (size_t)S * pixels, image = (size_t)b * pixels;
   const float K[4] = {intrins[b * 4 + 0], intrins[b * 4 + 1], intrins[b * 4 + 2], intrins[b * 4 + 3]};
-  nm::Sums m;
-  nm::clear_sums(m);
-  const nm::Sums* rec = reinterpret_cast<const nm::Sums*>(records) + (size_t)b * groups;
-  for (int r = t; r < groups; r += kThreads) nm::add_sums(m, rec[r]);
-  block_add(m, wave_part, part);
-  m.n_def = part[0]; m.np = part[1]; m.sp = part[2]; m.ns = part[3]; m.ss = part[4]; m.sg = part[5];
+  const nm::Sums m = sums::frame_sum<kThreads>(reinterpret_cast<const nm::Sums*>(records) + (size_t)b * groups, groups,
+                                              wave_part, part);
   const nm::Coef c = nm::finish(m, (double)prior_weight, (double)smooth_weight);
   if (blockIdx.x == 0 && t == 0) {
     loss[b] = (float)c.loss;
@@ -234,19 +202,9 @@ __global__ __launch_bounds__(kThreads) void normal_grad_kernel(Frame f, float pr
         const double vP[3] = {((l[0] - rr[0]) + up[0]) - dn[0], ((l[1] - rr[1]) + up[1]) - dn[1], ((l[2] - rr[2]) + up[2]) - dn[2]};
         dp::chain(nm::grad_z(u, v, K, vP), d, a, dp::kDepth, S, &vd, &va);
       }
-      for (int s = 0; s < S; ++s) {
-        v_depth_acc[frame + (size_t)s * pixels + p] = vd;
-        v_alphas[frame + (size_t)s * pixels + p] = va;
-      }
+      sums::store_pair(v_depth_acc, v_alphas, frame, pixels, p, S, vd, va);
     }
   }
-}
-
-bool shape_ok(int B, int S, int H, int W) {
-  if (B < 0 || S < 1 || H < 1 || W < 1) return false;
-  if ((long long)B * S > kMaxPlanes) return false;
-  const long long pixels = (long long)H * W;
-  return pixels < kMaxElems && (long long)(B > 0 ? B : 1) * S * pixels < kMaxElems;
 }
 
 int groups_x_of(int W) { return (W + kTileW * kGroupTiles - 1) / (kTileW * kGroupTiles); }
@@ -260,7 +218,7 @@ long long stash_bytes(int B, int H, int W) { return (long long)B * H * W * (long
 // see include/gsdeblur.h
 GS_EXPORT int gs_depth_normals(int B, int S, int H, int W, const float* depth_acc, const float* alphas,
                                const float* intrins, float min_alpha, float* normals_out, void* stream) {
-  if (!shape_ok(B, S, H, W) || !(min_alpha >= 0.0f)) return GS_ERR_INVALID;
+  if (!sums::shape_ok(B, S, H, W) || !(min_alpha >= 0.0f)) return GS_ERR_INVALID;
   if (B == 0) return GS_OK;
   if (!depth_acc || !alphas || !intrins || !normals_out) return GS_ERR_INVALID;
   const Frame f = {S, H, W, groups_x_of(W), min_alpha, 0.0f};
@@ -272,7 +230,7 @@ GS_EXPORT int gs_depth_normals(int B, int S, int H, int W, const float* depth_ac
 
 // see include/gsdeblur.h
 GS_EXPORT long long gs_normal_loss_workspace_bytes(int B, int S, int H, int W) {
-  if (!shape_ok(B, S, H, W)) return -1;
+  if (!sums::shape_ok(B, S, H, W)) return -1;
   return records_bytes(B, H, W) + stash_bytes(B, H, W) + (long long)B * H * W * 3 * (long long)sizeof(float);
 }
 
@@ -281,13 +239,14 @@ GS_EXPORT int gs_normal_loss(int B, int S, int H, int W, const float* depth_acc,
                              const float* prior, const float* guide, float prior_weight, float smooth_weight,
                              float edge_beta, float min_alpha, float* loss_out, double* stats_out, float* normals_out,
                              float* v_depth_acc, float* v_alphas, void* ws, long long ws_bytes, void* stream) {
-  if (!shape_ok(B, S, H, W)) return GS_ERR_INVALID;
+  if (!sums::shape_ok(B, S, H, W)) return GS_ERR_INVALID;
   if (!(min_alpha >= 0.0f) || !(edge_beta >= 0.0f) || !(prior_weight == prior_weight) || !(smooth_weight == smooth_weight))
     return GS_ERR_INVALID;
   if (B == 0) return GS_OK;
-  if (!depth_acc || !alphas || !intrins || !loss_out || !stats_out || !v_depth_acc || !v_alphas || !ws) return GS_ERR_INVALID;
-  if (((uintptr_t)ws & 7) || ((uintptr_t)stats_out & 7)) return GS_ERR_INVALID;
-  if (ws_bytes < gs_normal_loss_workspace_bytes(B, S, H, W)) return GS_ERR_WORKSPACE;
+  if (!intrins) return GS_ERR_INVALID;
+  const int ok = sums::check_loss_call(depth_acc, alphas, loss_out, stats_out, v_depth_acc, v_alphas, ws, ws_bytes,
+                                       gs_normal_loss_workspace_bytes(B, S, H, W));
+  if (ok != GS_OK) return ok;
   hipStream_t st = (hipStream_t)stream;
   char* base = reinterpret_cast<char*>(ws);
   double* records = reinterpret_cast<double*>(base);

@@ -24,12 +24,13 @@ from typing import Tuple
 import torch
 from torch import Tensor
 
+from . import _sums
+from ._sums import MAX_ELEMS, MAX_PLANES  # noqa: F401  (the limits of every loss on the sums)
+
 KINDS = ("pearson", "l1")            # csrc/depthprior_math.h kPearson, kL1
 SPACES = ("depth", "disparity")      # kDepth, kDisparity
 STATS = 8                            # kStats: n, sum x, sum y, sum xx, sum yy, sum xy, sum |x - y|, rho
 DEGENERATE_TOL = 1e-12               # kDegenerateTol
-MAX_PLANES = 256                     # B * S
-MAX_ELEMS = 1 << 30                  # B * S * H * W stays below it
 
 
 def _check(depth_acc, alphas, prior, kind, space, weight, min_alpha) -> Tuple[Tensor, Tensor, Tensor, bool]:
@@ -38,33 +39,19 @@ def _check(depth_acc, alphas, prior, kind, space, weight, min_alpha) -> Tuple[Te
         raise ValueError(f"unknown kind {kind!r} (one of {KINDS})")
     if space not in SPACES:
         raise ValueError(f"unknown space {space!r} (one of {SPACES})")
-    for name, t in (("depth_acc", depth_acc), ("alphas", alphas), ("prior", prior)):
-        if not isinstance(t, Tensor) or t.dtype != torch.float32:
-            raise ValueError(f"{name} must be a float32 tensor")
-        if t.device != depth_acc.device:
-            raise ValueError(f"{name} is on {t.device}, depth_acc on {depth_acc.device}")
-    if depth_acc.dim() not in (3, 4):
-        raise ValueError(f"depth_acc must be [S,H,W] or [B,S,H,W], got {tuple(depth_acc.shape)}")
-    if alphas.shape != depth_acc.shape:
-        raise ValueError(f"alphas must have depth_acc's shape {tuple(depth_acc.shape)}, got {tuple(alphas.shape)}")
-    single = depth_acc.dim() == 3
-    want = tuple(depth_acc.shape[1:]) if single else (depth_acc.shape[0],) + tuple(depth_acc.shape[2:])
+    if not isinstance(prior, Tensor):
+        raise ValueError("prior must be a float32 tensor")
+    depth_acc, alphas, single = _sums.check_sums("depth_prior_loss supports", depth_acc, alphas, prior=prior)
+    B, _, H, W = (int(s) for s in depth_acc.shape)
+    want = (H, W) if single else (B, H, W)
     if tuple(prior.shape) != want:
         raise ValueError(f"prior must be {list(want)}, got {tuple(prior.shape)}")
     if not float(min_alpha) >= 0.0:
         raise ValueError(f"min_alpha must be >= 0, got {min_alpha}")
     if not float(weight) == float(weight):
         raise ValueError("weight must be a number")
-    depth_acc, alphas, prior = depth_acc.detach(), alphas.detach(), prior.detach()
-    if single:
-        depth_acc, alphas, prior = depth_acc[None], alphas[None], prior[None]
-    B, S, H, W = (int(s) for s in depth_acc.shape)
-    if S < 1 or H < 1 or W < 1:
-        raise ValueError(f"depth_acc needs at least one sample and one pixel, got {tuple(depth_acc.shape)}")
-    if B * S > MAX_PLANES or max(B, 1) * S * H * W >= MAX_ELEMS:
-        raise ValueError(f"depth_prior_loss supports B * S <= {MAX_PLANES} and B * S * H * W < 2^30, got B={B}, S={S}, "
-                         f"H={H}, W={W}")
-    return depth_acc, alphas, prior, single
+    prior = prior.detach()
+    return depth_acc, alphas, prior[None] if single else prior, single
 
 
 # --------------------------------------------------------------------------- #
@@ -74,33 +61,18 @@ def depth_prior_loss_hip(depth_acc: Tensor, alphas: Tensor, prior: Tensor, kind:
                          weight: float = 1.0, min_alpha: float = 0.0) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
     """gs_depth_prior_loss on GPU tensors: depth_acc, alphas [B,S,H,W], prior [B,H,W] -> (loss [B], stats float64 [B,8],
     v_depth_acc [B,S,H,W], v_alphas [B,S,H,W])"""
-    from . import _lib
-    if not isinstance(depth_acc, Tensor) or not depth_acc.is_cuda:
-        raise ValueError("depth_acc must be a CUDA(HIP) tensor: the HIP path has no CPU fallback")
-    if depth_acc.dim() != 4:
-        raise ValueError(f"depth_acc must be [B,S,H,W], got {tuple(depth_acc.shape)}")
-    depth_acc, alphas, prior, _ = _check(depth_acc, alphas, prior, kind, space, weight, min_alpha)
+    _sums.check_hip(depth_acc)
+    return _launch(*_check(depth_acc, alphas, prior, kind, space, weight, min_alpha)[:3], kind, space, weight, min_alpha)
+
+
+def _launch(depth_acc, alphas, prior, kind, space, weight, min_alpha):
+    """depth_prior_loss_hip on what _check returned"""
     depth_acc, alphas, prior = depth_acc.contiguous(), alphas.contiguous(), prior.contiguous()
-    B, S, H, W = (int(s) for s in depth_acc.shape)
-    dev = depth_acc.device
-    loss = torch.empty(B, dtype=torch.float32, device=dev)
-    stats = torch.empty(B, STATS, dtype=torch.float64, device=dev)
-    v_depth_acc, v_alphas = torch.empty_like(depth_acc), torch.empty_like(alphas)
-    if B == 0:
-        return loss, stats, v_depth_acc, v_alphas
-    lib = _lib.load()
     vp = ctypes.c_void_p
-    with torch.cuda.device(dev):
-        ws_bytes = int(lib.gs_depth_prior_workspace_bytes(B, S, H, W))
-        if ws_bytes < 0:
-            raise _lib.HipLibraryError(f"depth_prior_loss: unsupported shape B={B}, S={S}, H={H}, W={W}")
-        ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=dev)
-        _lib.check(lib.gs_depth_prior_loss(B, S, H, W, vp(depth_acc.data_ptr()), vp(alphas.data_ptr()),
-                                           vp(prior.data_ptr()), KINDS.index(kind), SPACES.index(space), float(min_alpha),
-                                           float(weight), vp(loss.data_ptr()), vp(stats.data_ptr()),
-                                           vp(v_depth_acc.data_ptr()), vp(v_alphas.data_ptr()), vp(ws.data_ptr()),
-                                           ws_bytes, vp(torch.cuda.current_stream().cuda_stream)), "depth_prior_loss")
-    return loss, stats, v_depth_acc, v_alphas
+    return _sums.launch_loss("depth_prior_loss", "gs_depth_prior_workspace_bytes", depth_acc, alphas, STATS,
+                             lambda lib, head, outs, tail: lib.gs_depth_prior_loss(
+                                 *head, vp(prior.data_ptr()), KINDS.index(kind), SPACES.index(space), float(min_alpha),
+                                 float(weight), *outs, *tail))
 
 
 # --------------------------------------------------------------------------- #
@@ -115,11 +87,7 @@ def depth_prior_loss_torch(depth_acc: Tensor, alphas: Tensor, prior: Tensor, kin
     B, S, H, W = (int(s) for s in acc4.shape)
     dev = acc4.device
     f32 = dict(dtype=torch.float32, device=dev)
-    d, a = acc4[:, 0], al4[:, 0]
-    for s in range(1, S):
-        d, a = d + acc4[:, s], a + al4[:, s]
-    Sf = torch.tensor(float(S), **f32)
-    d, a = d / Sf, a / Sf
+    d, a = _sums.sample_means(acc4, al4)
     valid = (pr3 > 0) & (a > torch.tensor(float(min_alpha), **f32))
     one = torch.ones((), **f32)
     if space == "disparity":
@@ -162,8 +130,7 @@ def depth_prior_loss_torch(depth_acc: Tensor, alphas: Tensor, prior: Tensor, kin
     v_al = ga[:, None].expand(B, S, H, W).contiguous()
     loss = loss.float()
     stats = torch.stack([n, sx, sy, sxx, syy, sxy, sabs, rho], dim=1)
-    if single:
-        loss, v_acc, v_al, stats = loss[0], v_acc[0], v_al[0], stats[0]
+    loss, v_acc, v_al, stats = _sums.unbatch((loss, v_acc, v_al, stats), single)
     return (loss, v_acc, v_al, stats) if return_stats else (loss, v_acc, v_al)
 
 
@@ -183,27 +150,8 @@ def depth_prior_loss_with_grad(depth_acc: Tensor, alphas: Tensor, prior: Tensor,
     if not depth_acc.is_cuda:
         return depth_prior_loss_torch(depth_acc, alphas, prior, kind, space, weight, min_alpha, return_stats)
     acc4, al4, pr3, single = _check(depth_acc, alphas, prior, kind, space, weight, min_alpha)
-    loss, stats, v_acc, v_al = depth_prior_loss_hip(acc4, al4, pr3, kind, space, weight, min_alpha)
-    if single:
-        loss, stats, v_acc, v_al = loss[0], stats[0], v_acc[0], v_al[0]
+    loss, stats, v_acc, v_al = _sums.unbatch(_launch(acc4, al4, pr3, kind, space, weight, min_alpha), single)
     return (loss, v_acc, v_al, stats) if return_stats else (loss, v_acc, v_al)
-
-
-class _DepthPriorLoss(torch.autograd.Function):
-    """the gradients come out of the forward call; backward scales them by the incoming gradient"""
-
-    @staticmethod
-    def forward(ctx, depth_acc, alphas, prior, kind, space, weight, min_alpha):
-        loss, v_acc, v_al = depth_prior_loss_with_grad(depth_acc, alphas, prior, kind, space, weight, min_alpha)
-        ctx.save_for_backward(v_acc, v_al)
-        return loss
-
-    @staticmethod
-    def backward(ctx, v_loss):
-        v_acc, v_al = ctx.saved_tensors
-        scale = v_loss if v_loss.dim() == 0 else v_loss.reshape(-1, 1, 1, 1)
-        return (v_acc * scale if ctx.needs_input_grad[0] else None, v_al * scale if ctx.needs_input_grad[1] else None,
-                None, None, None, None, None)
 
 
 def depth_prior_loss(depth_acc: Tensor, alphas: Tensor, prior: Tensor, kind: str = "pearson", space: str = "depth",
@@ -214,4 +162,5 @@ def depth_prior_loss(depth_acc: Tensor, alphas: Tensor, prior: Tensor, kind: str
     "depth" (x = d / a) or "disparity" (x = a / d, for a prior given as inverse depth); min_alpha: pixels whose mean alpha
     is not above it are left out.  With a rendered depth map instead of the sums pass depth_acc = depth * m, alphas = m
     for m = (accumulation > 0) as float, one sample: x is then the depth itself."""
-    return _DepthPriorLoss.apply(depth_acc, alphas, prior, kind, space, float(weight), float(min_alpha))
+    return _sums.SumsLoss.apply(depth_prior_loss_with_grad, depth_acc, alphas, prior, kind, space, float(weight),
+                                float(min_alpha))

@@ -27,39 +27,19 @@ from typing import Optional, Tuple
 import torch
 from torch import Tensor
 
+from . import _sums
+from ._sums import MAX_ELEMS, MAX_PLANES  # noqa: F401  (the limits of every loss on the sums)
+
 STATS = 6                            # csrc/normal_math.h kStats: normals, Np, sum(1 - n.m), Ns, sum g (1 - n_p.n_q), sum g
 MIN_L2 = 1e-30                       # kMinL2
-MAX_PLANES = 256                     # B * S
-MAX_ELEMS = 1 << 30                  # B * S * H * W stays below it
 
 
 def _check(depth_acc, alphas, intrins, prior=None, guide=None, prior_weight=1.0, smooth_weight=0.0, edge_beta=0.0,
            min_alpha=0.0) -> Tuple[Tensor, Tensor, Tensor, Optional[Tensor], Optional[Tensor], bool]:
     """-> (depth_acc [B,S,H,W], alphas, intrins float32 [B,4] on the CPU, prior [B,H,W,3] or None, guide or None, single),
     detached; ValueError for anything else"""
-    if not isinstance(depth_acc, Tensor) or depth_acc.dtype != torch.float32:
-        raise ValueError("depth_acc must be a float32 tensor")
-    for name, t in (("alphas", alphas), ("prior", prior), ("guide", guide)):
-        if t is None and name != "alphas":
-            continue
-        if not isinstance(t, Tensor) or t.dtype != torch.float32:
-            raise ValueError(f"{name} must be a float32 tensor")
-        if t.device != depth_acc.device:
-            raise ValueError(f"{name} is on {t.device}, depth_acc on {depth_acc.device}")
-    if depth_acc.dim() not in (3, 4):
-        raise ValueError(f"depth_acc must be [S,H,W] or [B,S,H,W], got {tuple(depth_acc.shape)}")
-    if alphas.shape != depth_acc.shape:
-        raise ValueError(f"alphas must have depth_acc's shape {tuple(depth_acc.shape)}, got {tuple(alphas.shape)}")
-    single = depth_acc.dim() == 3
-    depth_acc, alphas = depth_acc.detach(), alphas.detach()
-    if single:
-        depth_acc, alphas = depth_acc[None], alphas[None]
+    depth_acc, alphas, single = _sums.check_sums("the normal ops support", depth_acc, alphas, prior=prior, guide=guide)
     B, S, H, W = (int(s) for s in depth_acc.shape)
-    if S < 1 or H < 1 or W < 1:
-        raise ValueError(f"depth_acc needs at least one sample and one pixel, got {tuple(depth_acc.shape)}")
-    if B * S > MAX_PLANES or max(B, 1) * S * H * W >= MAX_ELEMS:
-        raise ValueError(f"the normal ops support B * S <= {MAX_PLANES} and B * S * H * W < 2^30, got B={B}, S={S}, H={H}, "
-                         f"W={W}")
     images = []
     for name, t in (("prior", prior), ("guide", guide)):
         if t is not None:
@@ -97,17 +77,10 @@ def _device_intrins(K: Tensor, dev) -> Tensor:
     return _device_intrins_cached(tuple(K.reshape(-1).tolist()), int(K.shape[0]), str(dev))
 
 
-def _hip_inputs(depth_acc):
-    if not isinstance(depth_acc, Tensor) or not depth_acc.is_cuda:
-        raise ValueError("depth_acc must be a CUDA(HIP) tensor: the HIP path has no CPU fallback")
-    if depth_acc.dim() != 4:
-        raise ValueError(f"depth_acc must be [B,S,H,W], got {tuple(depth_acc.shape)}")
-
-
 def depth_normals_hip(depth_acc: Tensor, alphas: Tensor, intrins, min_alpha: float = 0.0) -> Tensor:
     """gs_depth_normals on GPU tensors: depth_acc, alphas [B,S,H,W], intrins [B,4] -> normals [B,H,W,3]"""
     from . import _lib
-    _hip_inputs(depth_acc)
+    _sums.check_hip(depth_acc)
     depth_acc, alphas, K, _, _, _ = _check(depth_acc, alphas, intrins, min_alpha=min_alpha)
     depth_acc, alphas = depth_acc.contiguous(), alphas.contiguous()
     B, S, H, W = (int(s) for s in depth_acc.shape)
@@ -130,36 +103,26 @@ def normal_loss_hip(depth_acc: Tensor, alphas: Tensor, intrins, prior: Optional[
                     edge_beta: float = 0.0, min_alpha: float = 0.0) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
     """gs_normal_loss on GPU tensors: depth_acc, alphas [B,S,H,W], intrins [B,4], prior / guide [B,H,W,3] or None ->
     (loss [B], stats float64 [B,6], normals [B,H,W,3], v_depth_acc [B,S,H,W], v_alphas [B,S,H,W])"""
-    from . import _lib
-    _hip_inputs(depth_acc)
-    depth_acc, alphas, K, prior, guide, _ = _check(depth_acc, alphas, intrins, prior, guide, prior_weight, smooth_weight,
-                                                   edge_beta, min_alpha)
+    _sums.check_hip(depth_acc)
+    checked = _check(depth_acc, alphas, intrins, prior, guide, prior_weight, smooth_weight, edge_beta, min_alpha)
+    return _launch_loss(*checked[:5], prior_weight, smooth_weight, edge_beta, min_alpha)
+
+
+def _launch_loss(depth_acc, alphas, K, prior, guide, prior_weight, smooth_weight, edge_beta, min_alpha):
+    """normal_loss_hip on what _check returned"""
     depth_acc, alphas = depth_acc.contiguous(), alphas.contiguous()
     prior = None if prior is None else prior.contiguous()
     guide = None if guide is None else guide.contiguous()
-    B, S, H, W = (int(s) for s in depth_acc.shape)
+    B, _, H, W = (int(s) for s in depth_acc.shape)
     dev = depth_acc.device
-    loss = torch.empty(B, dtype=torch.float32, device=dev)
-    stats = torch.empty(B, STATS, dtype=torch.float64, device=dev)
     normals = torch.empty(B, H, W, 3, dtype=torch.float32, device=dev)
-    v_depth_acc, v_alphas = torch.empty_like(depth_acc), torch.empty_like(alphas)
-    if B == 0:
-        return loss, stats, normals, v_depth_acc, v_alphas
-    lib = _lib.load()
     vp = ctypes.c_void_p
-    with torch.cuda.device(dev):
-        K = _device_intrins(K, dev)
-        ws_bytes = int(lib.gs_normal_loss_workspace_bytes(B, S, H, W))
-        if ws_bytes < 0:
-            raise _lib.HipLibraryError(f"normal_loss: unsupported shape B={B}, S={S}, H={H}, W={W}")
-        ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=dev)
-        _lib.check(lib.gs_normal_loss(B, S, H, W, vp(depth_acc.data_ptr()), vp(alphas.data_ptr()), vp(K.data_ptr()),
-                                      vp(prior.data_ptr()) if prior is not None else None,
-                                      vp(guide.data_ptr()) if guide is not None else None, float(prior_weight),
-                                      float(smooth_weight), float(edge_beta), float(min_alpha), vp(loss.data_ptr()),
-                                      vp(stats.data_ptr()), vp(normals.data_ptr()), vp(v_depth_acc.data_ptr()),
-                                      vp(v_alphas.data_ptr()), vp(ws.data_ptr()), ws_bytes,
-                                      vp(torch.cuda.current_stream().cuda_stream)), "normal_loss")
+    loss, stats, v_depth_acc, v_alphas = _sums.launch_loss(
+        "normal_loss", "gs_normal_loss_workspace_bytes", depth_acc, alphas, STATS,
+        lambda lib, head, outs, tail: lib.gs_normal_loss(
+            *head, vp(_device_intrins(K, dev).data_ptr()), vp(prior.data_ptr()) if prior is not None else None,
+            vp(guide.data_ptr()) if guide is not None else None, float(prior_weight), float(smooth_weight), float(edge_beta),
+            float(min_alpha), *outs, vp(normals.data_ptr()), *tail))
     return loss, stats, normals, v_depth_acc, v_alphas
 
 
@@ -189,11 +152,7 @@ def _geometry(acc4: Tensor, al4: Tensor, K: Tensor, min_alpha: float):
     B, S, H, W = (int(s) for s in acc4.shape)
     dev = acc4.device
     f32 = dict(dtype=torch.float32, device=dev)
-    d, a = acc4[:, 0], al4[:, 0]
-    for s in range(1, S):
-        d, a = d + acc4[:, s], a + al4[:, s]
-    Sf = torch.tensor(float(S), **f32)
-    d, a = d / Sf, a / Sf
+    d, a = _sums.sample_means(acc4, al4)
     has = (a > torch.tensor(float(min_alpha), **f32)) & (d > 0)
     one = torch.ones((), **f32)
     z = torch.where(has, d, one) / torch.where(has, a, one)
@@ -296,8 +255,7 @@ def normal_loss_torch(depth_acc: Tensor, alphas: Tensor, intrins, prior: Optiona
     v_al = ga[:, None].expand(B, S, H, W).contiguous()
     loss = loss.float()
     stats = torch.stack([tot(defined.double()), n_p, s_p, n_s, s_s, s_g], dim=1)
-    if single:
-        loss, v_acc, v_al, stats, n = loss[0], v_acc[0], v_al[0], stats[0], n[0]
+    loss, v_acc, v_al, stats, n = _sums.unbatch((loss, v_acc, v_al, stats, n), single)
     return (loss, v_acc, v_al) + ((stats,) if return_stats else ()) + ((n,) if return_normals else ())
 
 
@@ -336,28 +294,9 @@ def normal_loss_with_grad(depth_acc: Tensor, alphas: Tensor, intrins, prior: Opt
                                  min_alpha, return_stats, return_normals)
     acc4, al4, K, pr4, gd4, single = _check(depth_acc, alphas, intrins, prior, guide, prior_weight, smooth_weight,
                                             edge_beta, min_alpha)
-    loss, stats, n, v_acc, v_al = normal_loss_hip(acc4, al4, K, pr4, gd4, prior_weight, smooth_weight, edge_beta, min_alpha)
-    if single:
-        loss, stats, n, v_acc, v_al = loss[0], stats[0], n[0], v_acc[0], v_al[0]
+    loss, stats, n, v_acc, v_al = _sums.unbatch(
+        _launch_loss(acc4, al4, K, pr4, gd4, prior_weight, smooth_weight, edge_beta, min_alpha), single)
     return (loss, v_acc, v_al) + ((stats,) if return_stats else ()) + ((n,) if return_normals else ())
-
-
-class _NormalLoss(torch.autograd.Function):
-    """the gradients come out of the forward call; backward scales them by the incoming gradient"""
-
-    @staticmethod
-    def forward(ctx, depth_acc, alphas, intrins, prior, guide, prior_weight, smooth_weight, edge_beta, min_alpha):
-        loss, v_acc, v_al = normal_loss_with_grad(depth_acc, alphas, intrins, prior, guide, prior_weight, smooth_weight,
-                                                  edge_beta, min_alpha)
-        ctx.save_for_backward(v_acc, v_al)
-        return loss
-
-    @staticmethod
-    def backward(ctx, v_loss):
-        v_acc, v_al = ctx.saved_tensors
-        scale = v_loss if v_loss.dim() == 0 else v_loss.reshape(-1, 1, 1, 1)
-        return (v_acc * scale if ctx.needs_input_grad[0] else None, v_al * scale if ctx.needs_input_grad[1] else None,
-                None, None, None, None, None, None, None)
 
 
 def normal_loss(depth_acc: Tensor, alphas: Tensor, intrins, prior: Optional[Tensor] = None, guide: Optional[Tensor] = None,
@@ -366,5 +305,5 @@ def normal_loss(depth_acc: Tensor, alphas: Tensor, intrins, prior: Optional[Tens
     """The normal loss (module docstring) of depth_acc, alphas [S,H,W]: a scalar; or of [B,S,H,W]: [B], one loss per frame.
     Differentiable in depth_acc and alphas (an autograd Function; intrins, prior and guide are constants).  Arguments as
     normal_loss_with_grad."""
-    return _NormalLoss.apply(depth_acc, alphas, intrins, prior, guide, float(prior_weight), float(smooth_weight),
-                             float(edge_beta), float(min_alpha))
+    return _sums.SumsLoss.apply(normal_loss_with_grad, depth_acc, alphas, intrins, prior, guide, float(prior_weight),
+                                float(smooth_weight), float(edge_beta), float(min_alpha))

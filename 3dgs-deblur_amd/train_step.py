@@ -10,10 +10,11 @@ device and the HIP side raises when the library is missing.
 """
 from __future__ import annotations
 
+import dataclasses
 import functools
 import math
 import os
-from typing import Dict, Optional
+from typing import Callable, Dict, List, Optional
 
 import torch
 import torch.nn.functional as F
@@ -95,7 +96,6 @@ def depth_loss(depth: Tensor, gt_depth: Tensor, depth_lambda: float) -> Tensor:
     return depth_lambda * (torch.abs(depth - gt_depth) * valid).sum() / n
 
 
-_metric_depth_loss = depth_loss          # train_step's depth_loss= keyword shadows the function inside it
 DEPTH_LOSSES = (None, "l1", "pearson")
 DEPTH_SPACES = ("depth", "disparity")
 
@@ -163,9 +163,50 @@ def _metric_depth_sums(depth_acc: Tensor, alphas: Tensor, gt_depth: Tensor, dept
     render_and_backward builds for grad_depth, for a sums callable that also carries another term"""
     from .model import expected_depth
     da, al = depth_acc.detach().requires_grad_(True), alphas.detach().requires_grad_(True)
-    dl = _metric_depth_loss(expected_depth(da, al), gt_depth, depth_lambda)
+    dl = depth_loss(expected_depth(da, al), gt_depth, depth_lambda)
     v_acc, v_al = torch.autograd.grad(dl, (da, al), allow_unused=True)
     return (dl.detach(), torch.zeros_like(da) if v_acc is None else v_acc, torch.zeros_like(al) if v_al is None else v_al)
+
+
+@dataclasses.dataclass
+class GeometryTerm:
+    """One loss on a camera's rendered geometry, in the two forms train_step's routes need"""
+    name: str                      # the key its value is logged under
+    on_sums: Callable              # (depth_acc, alphas [S,H,W]) -> (loss, v_depth_acc, v_alphas): the one-call route
+    on_map: Callable               # (depth, accumulation [H,W,1]) -> loss, differentiable: the autograd and batch routes
+    native_sums: bool = True       # False: on_sums is only an autograd chain around on_map (the metric L1)
+
+
+def geometry_terms(model: SplatfactoDeblurModel, camera: Camera, gt_image: Tensor, gt_depth: Optional[Tensor],
+                   depth_lambda: float, depth_kind: Optional[str], depth_space: str, gt_normal: Optional[Tensor],
+                   normal_lambda: float, normal_smooth_lambda: float, normal_edge_beta: float) -> List[GeometryTerm]:
+    """train_step's geometry keywords for ONE camera -> its terms, in the order every route adds them: the depth term
+    (gt_depth with depth_lambda > 0: the metric L1 for depth_kind None, else depthprior's loss of that kind), then the normal
+    term (gt_normal with normal_lambda > 0 and / or normal_smooth_lambda > 0; without a prior its weight reaches the op as
+    0.0).  A missing map gives no such term.  gt_image: the target at the render's resolution; it is the edge guide when
+    normal_edge_beta > 0.  The maps are moved to its device and follow the resolution schedule, the intrinsics are those
+    of the rescaled camera."""
+    d = model.downscale_factor()
+    terms = []
+    if gt_depth is not None and depth_lambda > 0:
+        gt = downscale_depth(gt_depth.to(gt_image.device, torch.float32), d)
+        if depth_kind is None:
+            terms.append(GeometryTerm("depth_loss", lambda acc, al: _metric_depth_sums(acc, al, gt, depth_lambda),
+                                      lambda depth, _accumulation: depth_loss(depth, gt, depth_lambda), native_sums=False))
+        else:
+            from .depthprior import depth_prior_loss_with_grad
+            prior, d_args = gt.reshape(gt.shape[0], gt.shape[1]), (depth_kind, depth_space, depth_lambda)
+            terms.append(GeometryTerm("depth_loss", lambda acc, al: depth_prior_loss_with_grad(acc, al, prior, *d_args),
+                                      lambda depth, accumulation: depth_prior_term(depth, accumulation, gt, *d_args)))
+    use_prior = gt_normal is not None and normal_lambda > 0
+    if use_prior or normal_smooth_lambda > 0:
+        from .normals import normal_loss_with_grad
+        normals = downscale_normals(gt_normal.to(gt_image.device, torch.float32), d) if use_prior else None
+        n_args = (_camera_intrins(model, camera), normals, gt_image if normal_edge_beta > 0 else None,
+                  normal_lambda if use_prior else 0.0, normal_smooth_lambda, normal_edge_beta)
+        terms.append(GeometryTerm("normal_loss", lambda acc, al: normal_loss_with_grad(acc, al, *n_args),
+                                  lambda depth, accumulation: normal_term(depth, accumulation, *n_args)))
+    return terms
 
 
 def scale_regularization(log_scales: Tensor, max_gauss_ratio: float = 10.0) -> Tensor:
@@ -211,6 +252,20 @@ def _mcmc_reg(model: SplatfactoDeblurModel) -> Optional[Tensor]:
     if not (cfg.opacity_reg or cfg.scale_reg):
         return None
     return mcmc_regularization(model.opacities, model.scales, cfg.opacity_reg, cfg.scale_reg)
+
+
+def _add_regularizers(model: SplatfactoDeblurModel, loss: Tensor) -> Tensor:
+    """loss + the scale, MCMC and grid-TV regularisers model.config switches on, as differentiable terms (the autograd and
+    batch routes; the one-call route runs its own backward per term)"""
+    if model.config.use_scale_regularization:
+        loss = loss + scale_regularization(model.scales)
+    reg = _mcmc_reg(model)
+    if reg is not None:
+        loss = loss + reg
+    tv = _grid_tv(model)
+    if tv is not None:
+        loss = loss + tv
+    return loss
 
 
 class SelectiveAdam(torch.optim.Optimizer):
@@ -389,44 +444,35 @@ def train_step(model: SplatfactoDeblurModel, optimizers: Dict[str, torch.optim.O
                depth_space: str = "depth", gt_normal: Optional[Tensor] = None, normal_lambda: float = 0.0,
                normal_smooth_lambda: float = 0.0, normal_edge_beta: float = 0.0) -> Dict[str, float]:
     """One training iteration: render (HIP) -> loss -> backward (HIP) -> [DP gradient all-reduce] -> Adam.
-    camera / gt_image (/ gt_depth) may be lists: B cameras rendered as one batch (model.get_outputs_batch), the loss
+    camera / gt_image (/ gt_depth / gt_normal) may be lists: B cameras rendered as one batch (_train_step_batch), the loss
     the mean over the cameras of the per-image loss, on the autograd route.
-    gt_depth [H,W,1] (scene units, 0 = no measurement) with depth_lambda > 0 adds depth_loss(out["depth"], gt_depth)
-    to the loss, on either route (the depth map follows the resolution schedule: downscale_depth).
-    depth_loss "pearson" / "l1" (None: the metric L1 above, unchanged): gt_depth is a depth PRIOR and the term is
-    depthprior.depth_prior_loss(kind=depth_loss, space=depth_space, weight=depth_lambda) — "pearson" for a monocular prior
-    known up to scale and shift, depth_space="disparity" for one given as inverse depth.  On the one-call route the op
-    takes the compositor's per-sample sums between the two halves (render_and_backward grad_depth_sums: no torch op for
-    the depth term), on the autograd and batch routes the rendered depth map (depth_prior_term).  Unknown names raise
-    ValueError before anything is launched.
+    The geometry keywords become one short list of terms per camera (geometry_terms: the depth term, then the normal term);
+    every term is added to the image loss and logged in "loss".  The one-call route runs them on the compositor's raw
+    per-sample sums between the two halves of the frame (render_and_backward grad_depth_sums: their gradients are added, no
+    torch op per term), except that a lone metric L1 travels as grad_depth, the chain on the depth map the step has always
+    built for it; the autograd and batch routes run them on the rendered depth map.  What each keyword adds:
+    gt_depth [H,W,1] (scene units, 0 = no measurement) with depth_lambda > 0: the depth term — depth_loss None: the metric
+    L1 (depth_loss()); "pearson" / "l1": gt_depth is a depth PRIOR and the term depthprior.depth_prior_loss(kind=depth_loss,
+    space=depth_space, weight=depth_lambda), "pearson" for a monocular prior known up to scale and shift,
+    depth_space="disparity" for one given as inverse depth.
     gt_normal [H,W,3] (a normal PRIOR in the camera frame, x right, y down, z forward; a zero vector = no value) with
-    normal_lambda > 0, and / or normal_smooth_lambda > 0 (which needs no prior), add normals.normal_loss of the normals of
-    the rendered depth: normal_lambda * mean(1 - n.m) + normal_smooth_lambda * mean over adjacent pairs of
-    g (1 - n_p.n_q), with gt_image as the edge guide of g when normal_edge_beta > 0.  The op takes the intrinsics of the
-    camera the frame is rendered with and the prior follows the resolution schedule (downscale_normals).  On the one-call
-    route it runs on the raw sums through the same grad_depth_sums callable as the depth term (their gradients are added),
-    on the other routes on the rendered depth map (normal_term).  With every normal keyword at its default the step is
-    what it was, bit for bit."""
+    normal_lambda > 0, and / or normal_smooth_lambda > 0 (which needs no prior): the normal term, normals.normal_loss =
+    normal_lambda * mean(1 - n.m) + normal_smooth_lambda * mean over adjacent pairs of g (1 - n_p.n_q) on the normals of
+    the rendered depth, with gt_image as the edge guide of g when normal_edge_beta > 0.
+    Unknown names and bad weights raise ValueError before anything is launched; with every geometry keyword at its default
+    the step is what it was, bit for bit."""
     _check_depth_prior(depth_loss, depth_space)
     _check_normal_term(gt_normal, normal_lambda, normal_smooth_lambda, normal_edge_beta)
     if isinstance(camera, (list, tuple)):
         return _train_step_batch(model, optimizers, list(camera), list(gt_image), ssim_lambda, allreduce,
                                  gt_depth, depth_lambda, depth_loss, depth_space, gt_normal, normal_lambda,
                                  normal_smooth_lambda, normal_edge_beta)
-    depth_kind, depth_loss = depth_loss, _metric_depth_loss      # below, depth_loss is the module's function again
     model.train()
     for o in optimizers.values():
         o.zero_grad(set_to_none=True)
     gt_image = downscale_image(gt_image, model.downscale_factor())     # num_downscales resolution schedule
-    use_depth = gt_depth is not None and depth_lambda > 0
-    if use_depth:
-        gt_depth = downscale_depth(gt_depth.to(gt_image.device, torch.float32), model.downscale_factor())
-    use_prior = gt_normal is not None and normal_lambda > 0
-    use_normal = use_prior or normal_smooth_lambda > 0
-    if use_normal:
-        intrins = _camera_intrins(model, camera)
-        gt_normal = downscale_normals(gt_normal.to(gt_image.device, torch.float32), model.downscale_factor()) if use_prior else None
-        guide = gt_image if normal_edge_beta > 0 else None
+    terms = geometry_terms(model, camera, gt_image, gt_depth, depth_lambda, depth_loss, depth_space, gt_normal, normal_lambda,
+                           normal_smooth_lambda, normal_edge_beta)
     if one_call_route(model):
         # forward + backward of the frame as ONE host call (model.render_and_backward -> step.render_step): the HIP loss
         # kernel's forward already produces d loss / d rgb, so it sits between the two halves as a plain callable
@@ -447,50 +493,25 @@ def train_step(model: SplatfactoDeblurModel, optimizers: Dict[str, torch.optim.O
             v_rgb, v_grids = bilagrid.slice_bwd(grids, rgb, grid_index, v)
             grids.grad = v_grids if grids.grad is None else grids.grad + v_grids
             return v_rgb
-        grad_depth = None
-        if use_depth:
-            def grad_depth(depth, _accumulation):
-                depth = depth.requires_grad_(True)
-                box["depth_loss"] = dl = depth_loss(depth, gt_depth, depth_lambda)
-                return torch.autograd.grad(dl, depth)[0]
-        if use_normal:
-            # the normal term starts from the raw sums too; a depth term that is on travels in the same callable, so that
-            # render_and_backward never sees both of its depth keywords
-            from .depthprior import depth_prior_loss_with_grad
-            from .normals import normal_loss_with_grad
 
-            def grad_depth_sums(depth_acc, alphas):
-                box["normal_loss"], v_acc, v_al = normal_loss_with_grad(
-                    depth_acc, alphas, intrins, gt_normal, guide, normal_lambda if use_prior else 0.0, normal_smooth_lambda,
-                    normal_edge_beta)
-                if use_depth and depth_kind is not None:
-                    box["depth_loss"], d_acc, d_al = depth_prior_loss_with_grad(
-                        depth_acc, alphas, gt_depth.reshape(gt_depth.shape[0], gt_depth.shape[1]), depth_kind, depth_space,
-                        depth_lambda)
-                elif use_depth:
-                    box["depth_loss"], d_acc, d_al = _metric_depth_sums(depth_acc, alphas, gt_depth, depth_lambda)
-                else:
-                    return v_acc, v_al
-                return d_acc + v_acc, d_al + v_al
-            rgb = model.render_and_backward(camera, grad_image, grad_depth_sums=grad_depth_sums)
-        elif use_depth and depth_kind is not None:
-            # the prior loss starts from the compositor's raw sums: one kernel pair between the two halves, no torch op
-            from .depthprior import depth_prior_loss_with_grad
-            prior = gt_depth.reshape(gt_depth.shape[0], gt_depth.shape[1])
+        def grad_depth(depth, accumulation):               # a lone term without a form of its own on the sums
+            depth = depth.requires_grad_(True)
+            box[terms[0].name] = dl = terms[0].on_map(depth, accumulation)
+            return torch.autograd.grad(dl, depth)[0]
 
-            def grad_depth_sums(depth_acc, alphas):
-                box["depth_loss"], v_acc, v_al = depth_prior_loss_with_grad(depth_acc, alphas, prior, depth_kind,
-                                                                            depth_space, depth_lambda)
-                return v_acc, v_al
-            rgb = model.render_and_backward(camera, grad_image, grad_depth_sums=grad_depth_sums)
-        else:
-            rgb = model.render_and_backward(camera, grad_image, grad_depth)
+        def grad_depth_sums(depth_acc, alphas):            # the terms in order, their gradient pairs added
+            total = None
+            for term in terms:
+                box[term.name], v_acc, v_al = term.on_sums(depth_acc, alphas)
+                total = (v_acc, v_al) if total is None else (total[0] + v_acc, total[1] + v_al)
+            return total
+        lone_map_term = len(terms) == 1 and not terms[0].native_sums
+        depth_kw = {} if not terms else {"grad_depth": grad_depth} if lone_map_term else {"grad_depth_sums": grad_depth_sums}
+        rgb = model.render_and_backward(camera, grad_image, **depth_kw)
         rgb = box.get("rgb", rgb)                          # the logged PSNR is of the corrected image
         loss = box["loss"]
-        if use_depth:
-            loss = loss + box["depth_loss"].detach()
-        if use_normal:
-            loss = loss + box["normal_loss"].detach()
+        for term in terms:
+            loss = loss + box[term.name].detach()
         if model.config.use_scale_regularization:
             reg = scale_regularization(model.scales)
             reg.backward()
@@ -507,33 +528,26 @@ def train_step(model: SplatfactoDeblurModel, optimizers: Dict[str, torch.optim.O
                 grids.grad = torch.zeros_like(grids)
             loss = loss + bilagrid.tv_fwd_bwd_hip(grids.detach(), float(model.config.bilateral_grid_tv_lambda), grids.grad)
     else:
-        out = model.get_outputs(camera, return_depth=True) if use_depth or use_normal else model.get_outputs(camera)
+        out = model.get_outputs(camera, return_depth=True) if terms else model.get_outputs(camera)
         rgb = out["rgb"].detach()
         loss = image_loss(out["rgb"], gt_image, ssim_lambda)
-        if use_depth and depth_kind is not None:
-            loss = loss + depth_prior_term(out["depth"], out["accumulation"], gt_depth, depth_kind, depth_space,
-                                           depth_lambda)
-        elif use_depth:
-            loss = loss + depth_loss(out["depth"], gt_depth, depth_lambda)
-        if use_normal:
-            loss = loss + normal_term(out["depth"], out["accumulation"], intrins, gt_normal, guide, normal_lambda,
-                                      normal_smooth_lambda, normal_edge_beta)
-        if model.config.use_scale_regularization:
-            loss = loss + scale_regularization(model.scales)
-        reg = _mcmc_reg(model)
-        if reg is not None:
-            loss = loss + reg
-        tv = _grid_tv(model)
-        if tv is not None:
-            loss = loss + tv
+        for term in terms:
+            loss = loss + term.on_map(out["depth"], out["accumulation"])
+        loss = _add_regularizers(model, loss)
         loss.backward()
+    return _finish_step(model, optimizers, allreduce, loss, lambda: F.mse_loss(rgb.clamp(0, 1), gt_image.clamp(0, 1)))
+
+
+def _finish_step(model: SplatfactoDeblurModel, optimizers, allreduce: Optional[str], loss: Tensor,
+                 mse: Callable[[], Tensor]) -> Dict[str, float]:
+    """what follows the backward of a step: [DP gradient all-reduce] -> Adam on the step's rows -> model.step -> the log
+    values.  mse: builds the mean squared error of the step's render(s), after the optimizers have been issued"""
     if allreduce is not None:
         _dp_allreduce(model, allreduce)
     optimizers_step(optimizers.values(), row_mask=selection_mask(model, optimizers.values(), allreduce))
     model.step += 1
     # ONE read-back for the step's two log values (each .item() is a stream synchronisation)
-    mse = F.mse_loss(rgb.clamp(0, 1), gt_image.clamp(0, 1))
-    loss_v, mse_v = torch.stack([loss.detach().reshape(()).float(), mse.float()]).tolist()
+    loss_v, mse_v = torch.stack([loss.detach().reshape(()).float(), mse().float()]).tolist()
     return {"loss": float(loss_v), "psnr": float("inf") if mse_v == 0 else -10.0 * math.log10(mse_v)}
 
 
@@ -554,57 +568,31 @@ def _train_step_batch(model: SplatfactoDeblurModel, optimizers, cameras, gt_imag
                       depth_space: str = "depth", gt_normals=None, normal_lambda: float = 0.0,
                       normal_smooth_lambda: float = 0.0, normal_edge_beta: float = 0.0) -> Dict[str, float]:
     """train_step for B cameras: one get_outputs_batch, loss = mean over the cameras of train_step's per-image loss
-    (image loss + optional depth loss + optional normal loss; the keywords as train_step's, gt_normals a list with None
-    for a camera without a prior), one autograd backward, one optimizer step"""
+    (image loss + the camera's geometry_terms; the keywords as train_step's, gt_depths / gt_normals lists with None for a
+    camera without that map), one autograd backward, one optimizer step"""
     _check_depth_prior(depth_loss, depth_space)
     _check_normal_term(gt_normals, normal_lambda, normal_smooth_lambda, normal_edge_beta)
-    depth_kind, depth_loss = depth_loss, _metric_depth_loss      # below, depth_loss is the module's function again
     if len(cameras) != len(gt_images) or not cameras:
         raise ValueError("train_step needs as many images as cameras")
     model.train()
     for o in optimizers.values():
         o.zero_grad(set_to_none=True)
-    d = model.downscale_factor()
-    gts = [downscale_image(g, d) for g in gt_images]
-    use_depth = gt_depths is not None and depth_lambda > 0
-    if use_depth:
-        gt_depths = [None if g is None else downscale_depth(g.to(gts[0].device, torch.float32), d) for g in gt_depths]
-    use_prior = gt_normals is not None and normal_lambda > 0
-    use_normal = use_prior or normal_smooth_lambda > 0
-    if use_prior:
-        gt_normals = [None if g is None else downscale_normals(g.to(gts[0].device, torch.float32), d) for g in gt_normals]
-    out = model.get_outputs_batch(cameras, return_depth=True) if use_depth or use_normal else model.get_outputs_batch(cameras)
+    B = len(cameras)
+    gts = [downscale_image(g, model.downscale_factor()) for g in gt_images]
+    terms = [geometry_terms(model, cameras[b], gts[b], None if gt_depths is None else gt_depths[b], depth_lambda, depth_loss,
+                            depth_space, None if gt_normals is None else gt_normals[b], normal_lambda, normal_smooth_lambda,
+                            normal_edge_beta) for b in range(B)]
+    out = model.get_outputs_batch(cameras, return_depth=True) if any(terms) else model.get_outputs_batch(cameras)
     losses = []
-    for b in range(len(cameras)):
+    for b in range(B):
         l_b = image_loss(out["rgb"][b], gts[b], ssim_lambda)
-        prior_b = gt_normals[b] if use_prior else None
-        if use_normal and (prior_b is not None or normal_smooth_lambda > 0):
-            l_b = l_b + normal_term(out["depth"][b], out["accumulation"][b], _camera_intrins(model, cameras[b]), prior_b,
-                                    gts[b] if normal_edge_beta > 0 else None, normal_lambda, normal_smooth_lambda,
-                                    normal_edge_beta)
-        if use_depth and gt_depths[b] is not None and depth_kind is not None:
-            l_b = l_b + depth_prior_term(out["depth"][b], out["accumulation"][b], gt_depths[b], depth_kind, depth_space,
-                                         depth_lambda)
-        elif use_depth and gt_depths[b] is not None:
-            l_b = l_b + depth_loss(out["depth"][b], gt_depths[b], depth_lambda)
+        for term in terms[b]:
+            l_b = l_b + term.on_map(out["depth"][b], out["accumulation"][b])
         losses.append(l_b)
-    loss = torch.stack([l.reshape(()) for l in losses]).mean()
-    if model.config.use_scale_regularization:
-        loss = loss + scale_regularization(model.scales)
-    reg = _mcmc_reg(model)
-    if reg is not None:
-        loss = loss + reg
-    tv = _grid_tv(model)
-    if tv is not None:
-        loss = loss + tv
+    loss = _add_regularizers(model, torch.stack([l.reshape(()) for l in losses]).mean())
     loss.backward()
-    if allreduce is not None:
-        _dp_allreduce(model, allreduce)
-    optimizers_step(optimizers.values(), row_mask=selection_mask(model, optimizers.values(), allreduce))
-    model.step += 1
-    mse = torch.stack([F.mse_loss(out["rgb"][b].detach().clamp(0, 1), gts[b].clamp(0, 1)) for b in range(len(cameras))]).mean()
-    loss_v, mse_v = torch.stack([loss.detach().reshape(()).float(), mse.float()]).tolist()
-    return {"loss": float(loss_v), "psnr": float("inf") if mse_v == 0 else -10.0 * math.log10(mse_v)}
+    return _finish_step(model, optimizers, allreduce, loss, lambda: torch.stack(
+        [F.mse_loss(out["rgb"][b].detach().clamp(0, 1), gts[b].clamp(0, 1)) for b in range(B)]).mean())
 
 
 # --------------------------------------------------------------------------- #
@@ -764,20 +752,15 @@ def train_scene(model: SplatfactoDeblurModel, scene, images, iterations: int, lr
     for it in range(first, iterations + 1):
         if not order:
             order = [scene.train_indices[j] for j in torch.randperm(len(scene.train_indices), generator=g).tolist()]
-        if batch_size > 1:
-            ids = [order.pop() for _ in range(min(batch_size, len(order)))]
-            gd = [depths[i] for i in ids] if depths is not None else None
-            gn = [normals[i] for i in ids] if normals is not None else None
-            h = train_step(model, optimizers, [scene.cameras[i] for i in ids], [images[i] for i in ids], ssim_lambda,
-                           gt_depth=gd, depth_lambda=depth_lambda, depth_loss=depth_loss, depth_space=depth_space,
-                           gt_normal=gn, **normal_kw)
-        else:
-            i = order.pop()
-            gd = depths[i] if depths is not None else None
-            gn = normals[i] if normals is not None else None
-            h = train_step(model, optimizers, scene.cameras[i], images[i], ssim_lambda, gt_depth=gd,
-                           depth_lambda=depth_lambda, depth_loss=depth_loss, depth_space=depth_space, gt_normal=gn,
-                           **normal_kw)
+        ids = [order.pop() for _ in range(min(max(batch_size, 1), len(order)))]
+
+        def take(seq):                                     # a batch takes lists, a single view the items themselves
+            if seq is None:
+                return None
+            return [seq[i] for i in ids] if batch_size > 1 else seq[ids[0]]
+        h = train_step(model, optimizers, take(scene.cameras), take(images), ssim_lambda, gt_depth=take(depths),
+                       depth_lambda=depth_lambda, depth_loss=depth_loss, depth_space=depth_space, gt_normal=take(normals),
+                       **normal_kw)
         if use_mcmc:
             M.step_callback(model, optimizers, it, densify)
         elif densify is not None:

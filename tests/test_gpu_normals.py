@@ -159,18 +159,19 @@ def _training_inputs(dev):
 NORMAL_KW = dict(normal_lambda=0.5, normal_smooth_lambda=0.3, normal_edge_beta=2.0)
 
 
-@pytest.mark.parametrize("with_depth", [False, True], ids=["normals", "normals+pearson"])
+@pytest.mark.parametrize("with_depth", [False, "pearson", "metric"], ids=["normals", "normals+pearson", "normals+metric"])
 def test_train_step_routes_agree_with_a_normal_prior(gs, dev, with_depth):
     """the one-call route (the op on the raw sums between the compositor halves) against the autograd route (the op on the
-    rendered depth map), two steps each, with a normal prior plus smoothness, alone and together with the Pearson depth
-    prior: the bounds of test_gpu_depthprior.py's route comparison"""
+    rendered depth map), two steps each, with a normal prior plus smoothness, alone, together with the Pearson depth
+    prior and together with the metric depth L1 (whose chain then runs on the sums too): the bounds of
+    test_gpu_depthprior.py's route comparison"""
     from gsdeblur_amd import train_step as T
     from test_gpu_depth_grad import _model_and_camera
     sc, cfg, cam = _model_and_camera(gs, dev, use_scale_regularization=True)
     target, prior, gt = _training_inputs(dev)
     kw = dict(NORMAL_KW, gt_normal=prior)
     if with_depth:
-        kw.update(gt_depth=gt, depth_lambda=0.5, depth_loss="pearson")
+        kw.update(gt_depth=gt, depth_lambda=0.5, depth_loss=None if with_depth == "metric" else with_depth)
     results = []
     saved = T.TRAIN_AUTOGRAD
     try:
