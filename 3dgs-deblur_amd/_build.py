@@ -39,6 +39,7 @@ SOURCES = [
     ("tsdf.hip", ["-ffp-contract=off"]),
     # depth-derived normals, normal-prior and smoothness loss (normals.py): float32 values round every operation
     ("normals.hip", ["-ffp-contract=off"]),
+    ("meshclean.hip", []),       # mesh clean-up: component labelling and floater removal (meshclean.py), integers only
     ("frame.hip", []),           # host-side frame orchestration (no kernels of its own)
 ]
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-fvisibility=hidden"]

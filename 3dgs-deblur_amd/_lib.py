@@ -114,6 +114,11 @@ _SIGS = {
     "gs_tsdf_mesh_emit": [_I, _I, _I, _F, _F, _F, _F, _P, _P, _F, _I, _I, _P, _P, _P, _P, _L, _P],
     "gs_depth_normals": [_I, _I, _I, _I, _P, _P, _P, _F, _P, _P],
     "gs_normal_loss": [_I, _I, _I, _I, _P, _P, _P, _P, _P, _F, _F, _F, _F, _P, _P, _P, _P, _P, _P, _L, _P],
+    "gs_mesh_components_round": [_I, _I, _P, _P, _I, _P, _P],
+    "gs_mesh_components_finish": [_I, _I, _P, _P, _P, _P, _L, _P],
+    "gs_mesh_components_table": [_I, _I, _I, _P, _P, _P, _P, _L, _P],
+    "gs_mesh_filter_plan": [_I, _I, _P, _P, _I, _I, _P, _P, _L, _P],
+    "gs_mesh_filter_emit": [_I, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _L, _P],
 }
 _SIGS_LL = {
     "gs_scan_workspace_bytes": [_L],
@@ -133,6 +138,7 @@ _SIGS_LL = {
     "gs_depth_prior_workspace_bytes": [_I, _I, _I, _I],
     "gs_tsdf_mesh_workspace_bytes": [_I, _I, _I],
     "gs_normal_loss_workspace_bytes": [_I, _I, _I, _I],
+    "gs_mesh_clean_workspace_bytes": [_I, _I],
 }
 
 _lib = None

@@ -946,6 +946,41 @@ int gs_normal_loss(int B, int S, int H, int W, const float* depth_acc, const flo
                    float min_alpha, float* loss_out, double* stats_out, float* normals_out, float* v_depth_acc,
                    float* v_alphas, void* ws, long long ws_bytes, void* stream);
 
+/* ---- mesh clean-up: connected components of a triangle mesh and the removal of small ones (csrc/meshclean_math.h states
+ * the graph, the rounds, the ranking and the survivor rule; meshclean.py drives it).  No allocation, no state; integer
+ * atomics only (atomicMin, atomicAdd), no workgroup waits on another; two runs agree bit for bit.
+ *
+ * faces [F,3] int32, labels [V] int32, counts 8 ints, all on the device.  1 <= V, 0 <= F.  Every kernel tests the three
+ * indices of a face against [0, V) before it uses them; a face that fails is left out and counts[4] (status) becomes 1.
+ * A label outside [0, V) met by finish makes it 2.  counts: [0] V', [1] F', [2] C, [3] kept, [4] status, [5] the number
+ * (round + 1) of the last round that hooked.
+ *
+ * gs_mesh_components_round(round): round 0 first sets labels[v] = v and counts = 0; then one hook launch over the faces
+ * and one compress launch over the vertices.  The caller reads counts[5] back after every round and stops when it is not
+ * round + 1; labels[v] is then the smallest vertex index of v's component.  round >= 8 * bit_length(V) + 8 is refused.
+ * gs_mesh_components_finish: faces and vertices per component and the table of the C components in ascending order of
+ * their label, left in ws; counts[2] = C.  gs_mesh_components_table copies the first C rows of that table out.
+ * gs_mesh_filter_plan (after finish, same ws): the components with at least one face are ranked by (face count
+ * descending, label ascending); keep_largest = K > 0 lets only the first min(K, C) through (0: all), of these the ones
+ * with fewer than min_faces faces are dropped; output positions of the surviving vertices and faces are left in ws,
+ * counts[0] = V', counts[1] = F', counts[3] = surviving components.  The caller reads counts back once, allocates
+ * verts_out [V',3] fp32, faces_out [F',3] int32, colors_out [V',3] fp32 (given exactly when colors is) and calls
+ * gs_mesh_filter_emit (same ws): surviving vertices and faces in their old relative order, faces re-indexed.  V' == 0 and
+ * F' == 0 launch nothing.  plan and emit need F >= 1.
+ * Anything else, or a null pointer where none is allowed, is GS_ERR_INVALID before any launch.  ws: 256-byte aligned,
+ * gs_mesh_clean_workspace_bytes(V, F) bytes (-1 on invalid arguments; 32 bytes per vertex and 4 per face). */
+long long gs_mesh_clean_workspace_bytes(int V, int F);
+int gs_mesh_components_round(int V, int F, const int* faces, int* labels, int round, int* counts, void* stream);
+int gs_mesh_components_finish(int V, int F, const int* faces, const int* labels, int* counts, void* ws, long long ws_bytes,
+                              void* stream);
+int gs_mesh_components_table(int V, int F, int C, int* roots, int* face_counts, int* vert_counts, const void* ws,
+                             long long ws_bytes, void* stream);
+int gs_mesh_filter_plan(int V, int F, const int* faces, const int* labels, int min_faces, int keep_largest, int* counts,
+                        void* ws, long long ws_bytes, void* stream);
+int gs_mesh_filter_emit(int V, int F, const float* verts, const int* faces, const float* colors, const int* labels,
+                        int V_out, int F_out, float* verts_out, int* faces_out, float* colors_out, const void* ws,
+                        long long ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,7 +10,10 @@ Every camera of the set is rendered sharp (exposure and readout 0 at its effecti
 set to the image's index so that a checkpoint's pose adjustment applies), depth and colour are fused into a TSDF volume
 (model.fuse_tsdf: the box of the means between the 2nd and 98th percentile, --resolution samples along its longest
 axis, truncation 4 voxels, pixels with accumulation below --min-alpha left out), and the zero level set is written as a
-binary PLY with vertex colours (gs.tsdf.write_mesh_ply).  Prints one JSON line: vertices, faces, volume dims, seconds."""
+binary PLY with vertex colours (gs.tsdf.write_mesh_ply).  --keep-largest K and --min-component-faces N remove small
+connected components first (gs.mesh_filter_components: the floaters of a splat model); both are off by default and the
+file is then what it was without them.  Prints one JSON line: vertices, faces, volume dims, seconds, and with either
+option on the components found and kept."""
 import argparse
 import json
 import sys
@@ -21,6 +24,15 @@ import torch
 
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 import gsdeblur_amd as gs  # noqa: E402
+
+
+def clean_mesh(verts, faces, colors, keep_largest=None, min_component_faces=None):
+    """-> (verts, faces, colors, what the JSON line gains): the mesh itself, untouched, with both options off"""
+    if keep_largest is None and min_component_faces is None:
+        return verts, faces, colors, {}
+    verts, faces, colors, stats = gs.mesh_filter_components(verts, faces, colors, min_faces=min_component_faces or 1,
+                                                            keep_largest=keep_largest, return_stats=True)
+    return verts, faces, colors, {"components": stats["components"], "kept": stats["kept"]}
 
 
 def main():
@@ -35,6 +47,8 @@ def main():
     ap.add_argument("--min-alpha", type=float, default=0.5)
     ap.add_argument("--depth-max", type=float, default=None)
     ap.add_argument("--min-weight", type=float, default=0.0, help="use only cells whose corners were seen more than this")
+    ap.add_argument("--keep-largest", type=int, default=None, help="keep only the K connected components with the most faces")
+    ap.add_argument("--min-component-faces", type=int, default=None, help="drop connected components with fewer faces")
     ap.add_argument("--blurred", action="store_true", help="fuse the renders as the model blurs them (default: sharp)")
     ap.add_argument("--device", default="cuda:0")
     args = ap.parse_args()
@@ -56,9 +70,11 @@ def main():
     volume = model.fuse_tsdf(cameras, resolution=args.resolution, min_alpha=args.min_alpha, depth_max=args.depth_max,
                              sharp=not args.blurred)
     verts, faces, colors = gs.tsdf_extract_mesh(volume, min_weight=args.min_weight)
+    verts, faces, colors, cleaned = clean_mesh(verts, faces, colors, args.keep_largest, args.min_component_faces)
     gs.tsdf.write_mesh_ply(args.out, verts, faces, colors)
     print(json.dumps({"vertices": int(verts.shape[0]), "faces": int(faces.shape[0]), "dims": list(volume.dims),
-                      "voxel_size": volume.voxel_size, "views": len(cameras), "seconds": round(time.time() - t0, 3)}))
+                      "voxel_size": volume.voxel_size, "views": len(cameras), "seconds": round(time.time() - t0, 3),
+                      **cleaned}))
 
 
 if __name__ == "__main__":
