@@ -126,8 +126,14 @@ class _RowOps:
             n = len(grads)
             self._ptrs = (ctypes.c_void_p * n)(*[g.data_ptr() for g in grads])
             self._w = (ctypes.c_int * n)(*self.widths)
-            self._stream = ctypes.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
             self._vp = ctypes.c_void_p
+
+    @property
+    def _stream(self):
+        """the stream current on the gradients' device at EACH call: the buffers of a call (mask, payload, prefix sum)
+        are torch allocations and torch ops on that stream, so the launch between them has to be on it too — an object
+        built under one stream and used under another follows its caller, it does not remember where it was built"""
+        return self._vp(torch.cuda.current_stream(self.dev).cuda_stream)
 
     def _raw_write(self) -> None:
         """the kernels below write other ranks' rows into the gradients through raw pointers (no version bump): a

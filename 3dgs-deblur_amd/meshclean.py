@@ -180,7 +180,6 @@ class _Run:
         self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device=self.dev)
         self.labels = torch.empty(V, dtype=torch.int32, device=self.dev)
         self.counts = torch.empty(COUNT_WORDS, dtype=torch.int32, device=self.dev)
-        self.stream = vp(torch.cuda.current_stream().cuda_stream)
         self.p_faces, self.p_labels, self.p_counts = vp(self.faces.data_ptr()), vp(self.labels.data_ptr()), vp(self.counts.data_ptr())
         self.p_ws = vp(self.ws.data_ptr())
         self.rounds, guard = 0, max_rounds(V)
@@ -194,6 +193,12 @@ class _Run:
                 break
         self.check(self.lib.gs_mesh_components_finish(V, self.F, self.p_faces, self.p_labels, self.p_counts, self.p_ws,
                                                       self.ws_bytes, self.stream), what + " finish")
+
+    @property
+    def stream(self):
+        """the stream current on the mesh's device at EACH launch, never one remembered from construction: the run's
+        buffers and read-backs are torch's, on the current stream, and every launch goes where they are"""
+        return ctypes.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
 
     def read_counts(self):
         """the one read-back of the final counts; the status word becomes the error it stands for"""

@@ -534,19 +534,45 @@ def _band_edges(img_height: int, rs_bands: int, device) -> Tensor:
 
 
 _band_done_cache = {}
+_upload_streams = {}    # device -> the binding's own stream for blocking uploads of cached tables
+
+
+def _upload_blocking(host: Tensor, dev) -> Tensor:
+    """host tensor -> device tensor that is COMPLETE on the device when this returns, without waiting for the caller's
+    stream: a blocking copy (pageable source) on a stream of the binding's own that holds nothing else.  For tensors
+    that a cache hands to every stream.  (A blocking copy on the caller's stream is as safe, but the host then waits out
+    whatever that stream has queued; device ops on the caller's stream only QUEUE the tensor there, and a consumer on
+    another stream can read it before it is written.)"""
+    dev = torch.device(dev)
+    if dev.type != "cuda":
+        return host.to(dev)
+    with _state_lock:
+        st = _upload_streams.get(str(dev))
+        if st is None:
+            st = _upload_streams[str(dev)] = torch.cuda.Stream(dev)
+    with torch.cuda.stream(st):
+        return host.to(dev)                              # non_blocking=False: returns after the copy has finished
 
 
 def _band_tile_done(S: int, R: int, ty: int, tx: int, dev) -> Tensor:
     """u8 [S*R*ty*tx]: 1 for every tile of sub-pose (s, r) outside band r's tile rows — the initial tile_done of a
-    rolling-shutter frame.  Cached (a dozen small torch ops per frame otherwise, behind the plan read-back)."""
+    rolling-shutter frame.  Cached (a dozen small torch ops per frame otherwise, behind the plan read-back).
+    The cache is shared by every stream, so the tensor is built on the HOST and uploaded by _upload_blocking: it is
+    complete on the device when this returns, whichever stream asks for it next."""
     key = (S, R, ty, tx, str(dev))
     t = _band_done_cache.get(key)
     if t is None:
         e = [(r * ty) // R for r in range(R + 1)]       # same formula as _band_edges
-        rows = torch.arange(ty, device=dev)
+        rows = torch.arange(ty)
         band_open = torch.stack([(rows >= e[r]) & (rows < e[r + 1]) for r in range(R)])          # [R, ty]
-        t = (~band_open).to(torch.uint8)[None, :, :, None].expand(S, R, ty, tx).reshape(-1).contiguous()
+        host = (~band_open).to(torch.uint8)[None, :, :, None].expand(S, R, ty, tx).reshape(-1).contiguous()
+        t = _upload_blocking(host, dev)
         if len(_band_done_cache) > 16:
+            if t.is_cuda:
+                # the tables live in the upload stream's allocator pool and are read on other streams without
+                # record_stream: that is safe only because the cache keeps them alive and this eviction waits for
+                # the device before it frees them (a frame in flight on any stream may still read a dropped table)
+                torch.cuda.synchronize(t.device)
             _band_done_cache.clear()
         _band_done_cache[key] = t
     return t
