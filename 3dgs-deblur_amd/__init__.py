@@ -33,6 +33,8 @@ from .knn import knn, knn_mean_distance  # noqa: F401
 from .tsdf import TSDFVolume, tsdf_integrate, tsdf_extract_mesh  # noqa: F401
 from . import meshclean  # noqa: F401
 from .meshclean import mesh_components, mesh_filter_components  # noqa: F401
+from . import meshdecimate  # noqa: F401
+from .meshdecimate import mesh_decimate  # noqa: F401
 from .normals import depth_normals, normal_loss, normal_loss_with_grad  # noqa: F401
 from .blurscore import blur_stats  # noqa: F401
 from .step import render_step  # noqa: F401

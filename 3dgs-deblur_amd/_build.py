@@ -40,6 +40,8 @@ SOURCES = [
     # depth-derived normals, normal-prior and smoothness loss (normals.py): float32 values round every operation
     ("normals.hip", ["-ffp-contract=off"]),
     ("meshclean.hip", []),       # mesh clean-up: component labelling and floater removal (meshclean.py), integers only
+    # mesh decimation (meshdecimate.py): the float64 quadric sums and the solve round every operation, as the host build's do
+    ("meshdecimate.hip", ["-ffp-contract=off"]),
     ("frame.hip", []),           # host-side frame orchestration (no kernels of its own)
 ]
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-fvisibility=hidden"]

@@ -119,6 +119,8 @@ _SIGS = {
     "gs_mesh_components_table": [_I, _I, _I, _P, _P, _P, _P, _L, _P],
     "gs_mesh_filter_plan": [_I, _I, _P, _P, _I, _I, _P, _P, _L, _P],
     "gs_mesh_filter_emit": [_I, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _L, _P],
+    "gs_mesh_decimate_plan": [_P],
+    "gs_mesh_decimate_emit": [_P],
 }
 _SIGS_LL = {
     "gs_scan_workspace_bytes": [_L],
@@ -139,6 +141,7 @@ _SIGS_LL = {
     "gs_tsdf_mesh_workspace_bytes": [_I, _I, _I],
     "gs_normal_loss_workspace_bytes": [_I, _I, _I, _I],
     "gs_mesh_clean_workspace_bytes": [_I, _I],
+    "gs_mesh_decimate_workspace_bytes": [_I, _I],
 }
 
 _lib = None

@@ -981,6 +981,43 @@ int gs_mesh_filter_emit(int V, int F, const float* verts, const int* faces, cons
                         int V_out, int F_out, float* verts_out, int* faces_out, float* colors_out, const void* ws,
                         long long ws_bytes, void* stream);
 
+/* ---- mesh decimation: vertex clustering on a grid of cell_size anchored at the world origin, one representative per
+ * cluster placed by its plane quadrics (csrc/meshdecimate_math.h states the cell, the cluster order, the representative
+ * and the face rule; meshdecimate.py drives it).  No allocation, no state, no float atomics, no workgroup waits on
+ * another; every word of ws is written before it is read: two runs agree bit for bit whatever ws held.
+ *
+ * The arguments travel in a descriptor, the stream as its last field.  1 <= V <= 2^30, 1 <= F <= (2^31 - 1) / 3; verts [V,3] fp32, faces [F,3]
+ * int32, colors [V,3] fp32 or NULL, cell_size > 0 and finite, counts 8 ints, all pointers on the device.  ws: 256-byte
+ * aligned, gs_mesh_decimate_workspace_bytes(V, F) bytes (a pure host call; -1 on sizes outside the limits).
+ * gs_mesh_decimate_plan does everything that decides the output sizes and leaves in counts: [0] V', [1] F', [2] the
+ * clusters, [3] the faces dropped as degenerate, [4] the faces dropped as duplicates (dedupe != 0), [5] status: 0, 1 (a
+ * face index outside [0, V); tested before it is used) or 2 (a coordinate that is not finite, or a cell index beyond
+ * +-2^30).  With a status the other words mean nothing.  plan reads neither the outputs nor V_out / F_out.
+ * gs_mesh_decimate_emit (same descriptor, same ws, V_out = V', F_out = F' as read back) writes verts_out [V',3] fp32,
+ * colors_out [V',3] fp32 (NULL, or given with colors), faces_out [F',3] int32 and cluster_of [V] int32 (NULL, or the
+ * output vertex of every input vertex, -1 where its cluster was dropped).  verts_out may be NULL when V' == 0, faces_out
+ * when F' == 0.  Anything else is GS_ERR_INVALID before any launch, a short ws GS_ERR_WORKSPACE. */
+typedef struct gs_mesh_decimate_desc {
+  int V, F;
+  const float* verts;
+  const int* faces;
+  const float* colors;
+  double cell_size;
+  int dedupe;
+  int* counts;
+  void* ws;
+  long long ws_bytes;
+  float* verts_out;
+  int* faces_out;
+  float* colors_out;
+  int* cluster_of;
+  int V_out, F_out;
+  void* stream;
+} gs_mesh_decimate_desc;
+long long gs_mesh_decimate_workspace_bytes(int V, int F);
+int gs_mesh_decimate_plan(const gs_mesh_decimate_desc* d);
+int gs_mesh_decimate_emit(const gs_mesh_decimate_desc* d);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,8 +12,14 @@ set to the image's index so that a checkpoint's pose adjustment applies), depth 
 axis, truncation 4 voxels, pixels with accumulation below --min-alpha left out), and the zero level set is written as a
 binary PLY with vertex colours (gs.tsdf.write_mesh_ply).  --keep-largest K and --min-component-faces N remove small
 connected components first (gs.mesh_filter_components: the floaters of a splat model); both are off by default and the
-file is then what it was without them.  Prints one JSON line: vertices, faces, volume dims, seconds, and with either
-option on the components found and kept."""
+file is then what it was without them.  --decimate-cell S and --target-faces N then decimate the mesh by vertex
+clustering (gs.mesh_decimate): at cell size S, or at the first size of the ladder above the volume's voxel size (above S
+when both are given) that leaves at most N faces; both off: nothing runs.  The order is extract, clean, decimate:
+
+  python tools/export_mesh.py --checkpoint ck.pt --data /tmp/ds --out mesh.ply --keep-largest 1 --target-faces 100000
+
+Prints one JSON line: vertices, faces, volume dims, seconds, with a clean-up option on the components found and kept, and
+with a decimation option on the cell size used, the clusters and the faces before decimation."""
 import argparse
 import json
 import sys
@@ -35,6 +41,16 @@ def clean_mesh(verts, faces, colors, keep_largest=None, min_component_faces=None
     return verts, faces, colors, {"components": stats["components"], "kept": stats["kept"]}
 
 
+def decimate_mesh(verts, faces, colors, voxel_size, decimate_cell=None, target_faces=None):
+    """-> (verts, faces, colors, what the JSON line gains): the mesh itself, untouched, with both options off"""
+    if decimate_cell is None and target_faces is None:
+        return verts, faces, colors, {}
+    verts, faces, colors, stats = gs.mesh_decimate(verts, faces, colors, cell_size=voxel_size if decimate_cell is None else decimate_cell,
+                                                   target_faces=target_faces, return_stats=True)
+    return verts, faces, colors, {"decimate_cell": stats["cell_size"], "clusters": stats["clusters"],
+                                  "faces_before_decimation": stats["faces_in"]}
+
+
 def main():
     ap = argparse.ArgumentParser()
     src = ap.add_mutually_exclusive_group(required=True)
@@ -49,6 +65,9 @@ def main():
     ap.add_argument("--min-weight", type=float, default=0.0, help="use only cells whose corners were seen more than this")
     ap.add_argument("--keep-largest", type=int, default=None, help="keep only the K connected components with the most faces")
     ap.add_argument("--min-component-faces", type=int, default=None, help="drop connected components with fewer faces")
+    ap.add_argument("--decimate-cell", type=float, default=None, help="decimate by vertex clustering at this cell size")
+    ap.add_argument("--target-faces", type=int, default=None,
+                    help="decimate to at most this many faces (cell sizes from the voxel size, or --decimate-cell, upwards)")
     ap.add_argument("--blurred", action="store_true", help="fuse the renders as the model blurs them (default: sharp)")
     ap.add_argument("--device", default="cuda:0")
     args = ap.parse_args()
@@ -71,10 +90,12 @@ def main():
                              sharp=not args.blurred)
     verts, faces, colors = gs.tsdf_extract_mesh(volume, min_weight=args.min_weight)
     verts, faces, colors, cleaned = clean_mesh(verts, faces, colors, args.keep_largest, args.min_component_faces)
+    verts, faces, colors, decimated = decimate_mesh(verts, faces, colors, volume.voxel_size, args.decimate_cell,
+                                                    args.target_faces)
     gs.tsdf.write_mesh_ply(args.out, verts, faces, colors)
     print(json.dumps({"vertices": int(verts.shape[0]), "faces": int(faces.shape[0]), "dims": list(volume.dims),
                       "voxel_size": volume.voxel_size, "views": len(cameras), "seconds": round(time.time() - t0, 3),
-                      **cleaned}))
+                      **cleaned, **decimated}))
 
 
 if __name__ == "__main__":
